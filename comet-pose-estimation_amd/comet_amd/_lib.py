@@ -156,6 +156,10 @@ SIGNATURES = {
     "comet_maxpool2_nhwc": (_INT, [_INT, c_vp, c_vp, c_i64, _INT, _INT, _INT, c_vp]),
     "comet_sp_scores": (_INT, [c_vp, c_vp, _INT, _INT, _INT, c_vp]),
     "comet_maxfilt2d": (_INT, [c_vp, c_vp, c_vp, _INT, _INT, _INT, _INT, c_vp]),
+    "comet_sift_base": (_INT, [c_vp, c_vp, _INT, _INT, _INT, c_vp]),
+    "comet_gauss_blur": (_INT, [c_vp, c_vp, _INT, _INT, _INT, _F, c_vp]),
+    "comet_downsample2": (_INT, [c_vp, c_vp, _INT, _INT, _INT, c_vp]),
+    "comet_sift_detect": (_INT, [c_vp, _INT, _INT, _INT, _INT, _INT, _F, _F, _F, c_vp, _INT, c_vp, c_vp, c_vp]),
     "comet_gapr_fwd": (_INT, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, _INT, _INT, _F, _F, c_vp]),
     "comet_gapr_bwd": (_INT, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _INT, _INT,
                               _F, _F, c_vp]),

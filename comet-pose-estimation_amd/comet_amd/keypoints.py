@@ -17,14 +17,21 @@ Here:
   * filter_and_pad: the reference's rules, on the device, with the same torch RNG calls
     (torch.randint / torch.randperm on the keypoints' device) -- so a run seeded like the reference
     on the same device draws the same padding points -- and the 3x3 dilation on comet_maxfilt2d.
-  * SIFT: LightGlue's SIFT wraps OpenCV / pycolmap, neither of which exists here; `sift=None`
-    uses the SuperPoint keypoints alone.
+  * SIFT: LightGlue's SIFT wraps OpenCV's CPU detector (neither OpenCV nor pycolmap exists here).
+    `SIFT` is that detector's algorithm on the device (csrc/sift.hip: comet_sift_base,
+    comet_gauss_blur, comet_downsample2, comet_sift_detect -- Gaussian scale space, DoG extrema,
+    sub-pixel refinement, contrast and edge tests, orientation-peak count), followed by OpenCV's
+    keep-best-n and the wrapper's filter_dog_point / top-k as device torch ops; the loop builds it
+    when `train.track_by_sift` is set. `sift=None` uses the SuperPoint keypoints alone.
 Parity: the NMS and filter_and_pad are pinned to fixtures generated from the reference tree
 (glue-factory's batched_nms = LightGlue's simple_nms; the reference's filter_and_pad), and the
 network + keypoint selection to the reference tree's copy of the same magicleap network
 (gluefactory_nonfree/superpoint.py) run with PRNG weights (the trained superpoint_v1.pth is a
-download that is not available here); SIFT stays unpinned (absent).
+download that is not available here); SIFT is pinned to a float64 restatement of OpenCV's rules
+(tests/sift_numpy.py) and an analytic blob check -- parity with OpenCV itself is unmeasured.
 """
+import math
+
 import torch
 import torch.nn as nn
 
@@ -168,6 +175,177 @@ class SuperPoint(nn.Module):
         scale = torch.tensor([OW / W, OH / H], device=kp.device, dtype=kp.dtype)
         kp = (kp + 0.5) / scale - 0.5
         return {"keypoints": kp[None], "keypoint_scores": sc[None]}
+
+
+class SIFT(nn.Module):
+    """LightGlue's SIFT extractor (`backend="opencv"`: cv2.SIFT_create + detectAndCompute behind a
+    device-to-host copy) as a device-side difference-of-Gaussians detector on libcomet_hip.so
+    (csrc/sift.hip). No parameters, no descriptors, no orientation angles: COMET reads only the
+    keypoint coordinates.
+
+    The wrapper hands its `num_octaves` to OpenCV as nOctaveLayers (gluefactory sift.py:129); that is
+    reproduced on purpose: `num_octaves` (default 4) is the number of layers per octave, and the
+    number of octaves is OpenCV's own, round(log2(min(H, W)) - 2) + 1 with H, W the size of the 2x
+    up-sampled base image (first octave -1).
+
+    The steps follow OpenCV's detector rule by rule; they are pinned to a float64
+    restatement of those rules (tests/sift_numpy.py), not to OpenCV itself, which cannot be run where
+    this is built and tested."""
+
+    default_conf = {"max_num_keypoints": 4096, "detection_threshold": 0.0066667, "edge_threshold": 10,
+                    "num_octaves": 4, "nms_radius": 0, "resize": 1024, "candidate_capacity": 32768}
+    sigma = 1.6
+
+    def __init__(self, **conf):
+        super().__init__()
+        unknown = set(conf) - set(self.default_conf)
+        if unknown:
+            raise ValueError(f"unknown SIFT options {sorted(unknown)}")
+        self.conf = {**self.default_conf, **conf}
+        mk = self.conf["max_num_keypoints"]
+        if mk is not None and mk <= 0:
+            raise ValueError("max_num_keypoints must be positive or None")
+        if not 1 <= self.conf["num_octaves"] <= 8:
+            raise ValueError("num_octaves (layers per octave) must be in 1..8")
+
+    def layer_sigmas(self):
+        """The blur that takes layer i - 1 of an octave to layer i (i = 1 .. layers + 2)."""
+        nl = self.conf["num_octaves"]
+        k = 2.0 ** (1.0 / nl)
+        return [((self.sigma * k ** i) ** 2 - (self.sigma * k ** (i - 1)) ** 2) ** 0.5 for i in range(1, nl + 3)]
+
+    @torch.no_grad()
+    def pyramid(self, gray):
+        """gray uint8 [B, H, W] -> one [B, layers + 3, h, w] f32 buffer of Gaussian images per octave.
+        Octaves without a pixel inside the detector's 5-px border are not built: nothing reads them."""
+        gray = gray.contiguous()
+        B, H, W = gray.shape
+        lib, st = L.load(), ops.stream()
+        nl = self.conf["num_octaves"]
+        n_oct = int(round(math.log2(min(2 * H, 2 * W)) - 2)) + 1
+        sig = self.layer_sigmas()
+        octaves = []
+        h, w = 2 * H, 2 * W
+        for o in range(n_oct):
+            if min(h, w) <= 10:
+                break
+            buf = torch.empty(B, nl + 3, h, w, device=gray.device, dtype=torch.float32)
+            layers = [torch.empty(B, h, w, device=gray.device, dtype=torch.float32) for _ in range(nl + 3)]
+            if o == 0:
+                L.check(lib.comet_sift_base(gray.data_ptr(), layers[0].data_ptr(), B, H, W, st), "comet_sift_base")
+            else:
+                ph, pw = prev.shape[-2:]
+                L.check(lib.comet_downsample2(prev.data_ptr(), layers[0].data_ptr(), B, ph, pw, st), "comet_downsample2")
+            for i in range(1, nl + 3):
+                L.check(lib.comet_gauss_blur(layers[i - 1].data_ptr(), layers[i].data_ptr(), B, h, w, sig[i - 1], st),
+                        "comet_gauss_blur")
+            torch.stack(layers, 1, out=buf)
+            octaves.append(buf)
+            prev = layers[nl]
+            h, w = h // 2, w // 2
+        return octaves
+
+    @torch.no_grad()
+    def detect(self, gray):
+        """gray uint8 [B, H, W] -> per image the candidate list before any cut: [n, 7] f32 rows
+        (x, y, size, response, orientation count, octave, layer), x / y / size in pixels of `gray`,
+        sorted by (response descending, octave, layer, y, x) -- the kernel appends candidates in the
+        order its atomic adds arrive, the sort makes the list independent of that."""
+        if gray.dtype != torch.uint8 or gray.dim() != 3:
+            raise ValueError("detect takes a uint8 [B, H, W] batch")
+        B = gray.shape[0]
+        lib, st = L.load(), ops.stream()
+        cap = int(self.conf["candidate_capacity"])
+        cand = torch.empty(B, cap, 8, device=gray.device, dtype=torch.float32)
+        count = torch.zeros(B + 1, device=gray.device, dtype=torch.int32)  # [B] counters, then the overflow flag
+        for o, buf in enumerate(self.pyramid(gray)):
+            h, w = buf.shape[-2:]
+            L.check(lib.comet_sift_detect(buf.data_ptr(), B, self.conf["num_octaves"], h, w, o,
+                                          float(self.conf["detection_threshold"]), float(self.conf["edge_threshold"]),
+                                          self.sigma, cand.data_ptr(), cap, count.data_ptr(),
+                                          count.data_ptr() + 4 * B, st), "comet_sift_detect")
+        n = count.tolist()
+        if n[B] != 0:
+            raise L.CometHipError(f"SIFT: more than candidate_capacity={cap} keypoints in one image "
+                                  f"(counts {n[:B]}); raise candidate_capacity")
+        out = []
+        for b in range(B):
+            c = cand[b, :n[b], :7]
+            order = torch.arange(c.shape[0], device=c.device)
+            for col, desc in ((0, False), (1, False), (6, False), (5, False), (3, True)):  # least significant key first
+                order = order[torch.sort(c[order, col], stable=True, descending=desc)[1]]
+            c = c[order].clone()
+            c[:, :3] *= 0.5  # the base image is the 2x up-sample (first octave -1)
+            out.append(c)
+        return out
+
+    def select(self, cand, H, W):
+        """Indices into a detect() list (sorted by response) of the keypoints extract() returns:
+        OpenCV's keep-best-n over the list with every candidate repeated once per orientation peak
+        (all ties with the last kept response stay), then the wrapper's filter_dog_point (one
+        keypoint per rounded pixel -- the best; equal scores: the first of the sorted list -- and the
+        (2 nms_radius + 1)^2 max filter), then the top max_num_keypoints by score."""
+        mk = self.conf["max_num_keypoints"]
+        resp, nori = cand[:, 3], cand[:, 4]
+        idx = torch.nonzero(nori > 0)[:, 0]
+        if mk is not None and idx.numel() > 0:
+            cum = torch.cumsum(nori[idx], 0)
+            if cum[-1] > mk:
+                last = resp[idx][torch.searchsorted(cum, torch.tensor([float(mk)], device=cum.device))[0]]
+                idx = idx[resp[idx] >= last]
+        if idx.numel() == 0:
+            return idx
+        ij = torch.round(cand[idx, :2] - 0.5).long()
+        pix = ij[:, 1].clamp(0, H - 1) * W + ij[:, 0].clamp(0, W - 1)
+        ps, perm = torch.sort(pix, stable=True)
+        first = torch.ones_like(ps, dtype=torch.bool)
+        first[1:] = ps[1:] != ps[:-1]
+        keep = torch.sort(perm[first])[0]
+        idx, pix = idx[keep], pix[keep]
+        r = int(self.conf["nms_radius"] or 0)
+        if r > 0:
+            buf = torch.zeros(H * W, device=cand.device, dtype=torch.float32)
+            buf[pix] = resp[idx]
+            idx = idx[buf[pix] == _maxfilt(buf.view(1, H, W), r).view(-1)[pix]]
+        if mk is not None and idx.numel() > mk:
+            idx = idx[:mk]
+        return idx
+
+    @torch.no_grad()
+    def extract(self, img):
+        """LightGlue Extractor.extract for a batch: img [3, H, W] or [B, 3, H, W] in [0, 1] ->
+        {"keypoints" [B, N, 2] (x, y in input pixels), "keypoint_scores" [B, N], "scales" [B, N],
+        "num_keypoints" [B]}, best response first. N is the largest count of the batch; the rows
+        past an image's own count hold keypoints -1 and zeros."""
+        if img.dim() == 3:
+            img = img[None]
+        if img.dim() != 4 or img.shape[1] != 3:
+            raise ValueError("extract takes [3, H, W] or [B, 3, H, W]")
+        B, _, H, W = img.shape
+        r = self.conf["resize"]
+        if r is not None:  # resize so that the long side is `resize` (ImagePreprocessor side="long")
+            s = r / max(H, W)
+            OH, OW = int(round(H * s)), int(round(W * s))
+        else:
+            OH, OW = H, W
+        g = torch.empty(B, OH, OW, 1, device=img.device, dtype=torch.float32)
+        L.check(L.load().comet_sp_preprocess(L.F32, img.contiguous().float().data_ptr(), g.data_ptr(), B, H, W, OH, OW,
+                                             1, ops.stream()), "comet_sp_preprocess")
+        gray = (g.view(B, OH, OW) * 255.0).clamp_(0, 255).to(torch.uint8)  # sift.py:156, truncating
+        sel = []
+        for c in self.detect(gray):
+            sel.append(c[self.select(c, OH, OW)])
+        n = max(c.shape[0] for c in sel)
+        scale = torch.tensor([OW / W, OH / H], device=img.device, dtype=torch.float32)
+        kp = torch.full((B, n, 2), -1.0, device=img.device)
+        sc = torch.zeros(B, n, device=img.device)
+        sz = torch.zeros(B, n, device=img.device)
+        for b, c in enumerate(sel):
+            kp[b, :c.shape[0]] = (c[:, :2] + 0.5) / scale - 0.5
+            sc[b, :c.shape[0]] = c[:, 3]
+            sz[b, :c.shape[0]] = c[:, 2] / scale.mean()
+        num = torch.tensor([c.shape[0] for c in sel], device=img.device)
+        return {"keypoints": kp, "keypoint_scores": sc, "scales": sz, "num_keypoints": num}
 
 
 def sample_extra_points(mask, need_extra, device):

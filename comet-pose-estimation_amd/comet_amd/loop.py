@@ -4,8 +4,8 @@
                        seq_name, image_names, first_mask, R_matrix) on the device; default focal
                        cfg.default_focal_length and principal point (W/2, H/2) when absent
   train_or_eval_fn     train_eval_func_new_cp5.py:514-823, train and eval branches: keypoint
-                       tracks from frame 0 (track_by_spsg: SuperPoint, comet_amd.keypoints; SIFT is
-                       not available), QuaternionCameras from the batch (597-606),
+                       tracks from frame 0 (track_by_spsg: SuperPoint, plus the SIFT of
+                       comet_amd.keypoints when train.track_by_sift is set), QuaternionCameras from the batch (597-606),
                        model(..., training) (under no_grad for eval), loss.mean(), the eval block's
                        pose metrics (comet_amd.metrics.pose_metrics), Stats, then for training
                        zero_grad -> accelerator.backward -> clip_grad_norm_ -> optimizer.step ->
@@ -379,6 +379,15 @@ def _keypoint_init(cfg, device):
     return SuperPoint(max_num_keypoints=_get(cfg, "train.track_num", 512), detection_threshold=0.005).to(device).eval()
 
 
+def _sift_init(cfg, device):
+    """The reference's second detector, lightglue.SIFT(max_num_keypoints=track_num)
+    (train_eval_func_new_cp5.py:529-531), built only when train.track_by_sift is true."""
+    if not _get(cfg, "train.track_by_sift", False):
+        return None
+    from .keypoints import SIFT
+    return SIFT(max_num_keypoints=_get(cfg, "train.track_num", 512)).to(device).eval()
+
+
 def train_or_eval_fn(model, dataloader, cfg, optimizer, stats, accelerator, lr_scheduler, training=True, epoch=-1,
                      sp=None):
     """train_eval_func_new_cp5.py:514-823 (visualisation / demo-JSON branches excluded).
@@ -391,6 +400,7 @@ def train_or_eval_fn(model, dataloader, cfg, optimizer, stats, accelerator, lr_s
                 and not _get(cfg, "labor_input_traj", False))
     if spsg and sp is None:
         sp = _keypoint_init(cfg, dev)
+    sift = _sift_init(cfg, dev) if spsg else None
     acc5 = [0.0, 0.0, 0.0]
     for step, batch in enumerate(dataloader):
         (images, T_xyz, T_uvz, rotation, fl, pp, ratio, sel_first_name, image_names, mask,
@@ -399,7 +409,7 @@ def train_or_eval_fn(model, dataloader, cfg, optimizer, stats, accelerator, lr_s
         if spsg:
             from .keypoints import keypoint_tracks
             tracks, tracks_visibility = keypoint_tracks(sp, images, mask.to(dev).bool(), _get(cfg, "train.track_num", 512),
-                                                        sift=None, min_required=256, names=sel_first_name)
+                                                        sift=sift, min_required=256, names=sel_first_name)
         else:
             tracks, tracks_visibility = None, None
         gt_cameras = None

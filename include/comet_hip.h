@@ -479,6 +479,32 @@ int comet_sp_scores(const float* logits, float* scores, int B, int h, int w, voi
 int comet_maxfilt2d(const float* x, float* y, float* tmp, int B, int H, int W, int r, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * SIFT (difference-of-Gaussians) keypoint detector, the second detector of the keypoint
+ * initialisation (train_eval_func_new_cp5.py:527-531: lightglue SIFT = OpenCV's detector; the
+ * algorithm, not a bit copy: DESIGN.md §11). Images are contiguous [B, H, W]; one launch serves all B.
+ * comet_sift_base: gray uint8 [B,H,W] -> octave-0 base image f32 [B,2H,2W]: 2x bilinear up-sample
+ *   (src = (dst + 0.5) / 2 - 0.5, edge-clamped), then a blur of sigma = sqrt(1.6^2 - (2 * 0.5)^2).
+ * comet_gauss_blur: separable Gaussian blur of f32 [B,H,W] (x != y): radius r = (round(8 sigma + 1) | 1) / 2,
+ *   taps exp(-x^2 / 2 sigma^2) normalised to sum 1 (computed in double on the host), reflect-101
+ *   border. COMET_EINVAL when r > 10 (sigma > ~2.56), the halo the kernel's LDS tile holds.
+ * comet_downsample2: y [B,H/2,W/2] = every second pixel of every second row of x [B,H,W].
+ * comet_sift_detect: one octave. gauss = its n_layers + 3 Gaussian images [B, n_layers + 3, h, w].
+ *   Every DoG extremum inside the 5-px border that survives the sub-pixel refinement (at most 5
+ *   Newton steps), the contrast test (|contr| * n_layers >= contrast_threshold) and the edge test is
+ *   appended to cand [B, cap, 8] f32 (16-byte aligned) as (x, y, size, response, number of
+ *   orientation-histogram peaks, octave, layer, 0), x / y / size in base-image pixels
+ *   (x 2^octave). count [B] int32 (zeroed by the caller before the first octave) is advanced by
+ *   one atomic add per keypoint -- the order of the records is not defined; when an image has
+ *   more than cap keypoints, *overflow (int32, zeroed by the caller) is set and the surplus is
+ *   not written. sigma: the scale of layer 0 (1.6). */
+int comet_sift_base(const uint8_t* gray, float* base, int B, int H, int W, void* stream);
+int comet_gauss_blur(const float* x, float* y, int B, int H, int W, float sigma, void* stream);
+int comet_downsample2(const float* x, float* y, int B, int H, int W, void* stream);
+int comet_sift_detect(const float* gauss, int B, int n_layers, int h, int w, int octave,
+                      float contrast_threshold, float edge_threshold, float sigma, float* cand, int cap,
+                      int* count, int* overflow, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Debug support (bounds asserts and a NaN / Inf check mode).
  * comet_count_nonfinite: adds the number of NaN / Inf elements of x (n elements, dtype) to
  *   *count (an int32 on the device; no host sync). Used by comet_amd.debug's finite-check hooks.
