@@ -87,6 +87,12 @@ class AttnBwdArgs(ctypes.Structure):
     ]
 
 
+class RingTensor(ctypes.Structure):
+    _fields_ = [("src", c_vp), ("dst", c_vp), ("slot_bytes", c_i64)]
+
+
+RING_MAX_TENSORS = 4  # COMET_RING_MAX_TENSORS
+
 # (name, restype, argtypes); every exported symbol of include/comet_hip.h
 _F = ctypes.c_float
 _INT = ctypes.c_int
@@ -175,6 +181,7 @@ SIGNATURES = {
     "comet_refine_combine": (_INT, [c_vp, c_vp, c_vp, c_vp, c_i64, _INT, c_i64, c_vp]),
     "comet_track_score": (_INT, [_INT, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, _INT, c_i64, _INT, _INT, _INT, c_vp]),
     "comet_dino_prep": (_INT, [_INT, c_vp, c_vp, c_i64, _INT, _INT, _INT, _INT, c_i64, c_vp, c_vp, c_vp]),
+    "comet_ring_gather": (_INT, [ctypes.POINTER(RingTensor), _INT, c_vp, c_vp, _INT, _INT, _INT, c_vp]),
 }
 
 _lib = None

@@ -588,6 +588,68 @@ def train_fn(cfg, data_root=None, eval_only=True, csv_log=True):
 
 
 # ------------------------------------------------------------------------------------------------
+def sequence_stream(seq_dir):
+    """One YTDataset sequence directory (frames/frame_*, Mask/mask_*) as a stream: -> (iterator over
+    every frame in order, uint8 [H, W, 3] host arrays; the sequence's square crop box, computed as
+    YTDataset.load_host does but over all frames). Host only."""
+    from PIL import Image
+    from .data import make_bbox_square, mask_bbox
+    fdir, mdir = os.path.join(seq_dir, "frames"), os.path.join(seq_dir, "Mask")
+    names = sorted(f for f in os.listdir(fdir) if f.startswith("frame_"))
+    boxes = [mask_bbox(np.array(Image.open(os.path.join(mdir, m)).convert("L"), dtype=np.uint8))
+             for m in sorted(f for f in os.listdir(mdir) if f.startswith("mask_"))]
+    xmins, ymins, xmaxs, ymaxs = zip(*boxes)
+    bbox = np.array([min(xmins), min(ymins), max(xmaxs), max(ymaxs)], dtype=np.float64)
+    size = np.max([bbox[2] - bbox[0], bbox[3] - bbox[1]])
+    bbox = bbox + np.array([-1.0, -1.0, 1.0, 1.0]) * (size * 0.15)
+    box = tuple(int(v) for v in make_bbox_square(bbox, size * 1.3))
+    return (np.asarray(Image.open(os.path.join(fdir, n)).convert("RGB")) for n in names), box
+
+
+STREAM_FIELDS = ("frame_index", "newest_frame", "du", "dv", "dd", "qw", "qx", "qy", "qz", "hop_ms")
+
+
+def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, query_points=None, device="cuda"):
+    """Online evaluation of one long sequence (opt-in: cfg.stream.enable must be true; train_fn /
+    test_fn never call it). frames_iter yields uint8 [H, W, 3] frames in order (sequence_stream);
+    each is cropped to `box` and resized / normalised on the device (crop_resize_normalize, the
+    loader's pixel path) and pushed into a comet_amd.stream.PoseStream of cfg.stream.window
+    (default cfg.seqlen) frames, cfg.stream.stride (1) and cfg.stream.capacity (window). Query points:
+    `query_points` [N, 2] for every window, else SuperPoint (+ SIFT) keypoints of each window's first
+    frame. One CSV row per hop: the window's first frame, its newest frame, the newest frame's pose
+    encoding relative to the first (du, dv, dd, quaternion) and the time of the push that completed
+    the hop (per-frame stages of the new frame + the hop), from device events. -> number of hops."""
+    from .data import crop_resize_normalize
+    from .stream import PoseStream, keypoint_query
+    if not _get(cfg, "stream.enable", False):
+        raise ValueError("stream_eval is opt-in: set cfg.stream.enable")
+    model.eval()
+    window = int(_get(cfg, "stream.window", _get(cfg, "seqlen", 16)))
+    size = int(_get(cfg, "train.img_size", 512))
+    query_fn = None
+    if query_points is None:
+        sp = sp if sp is not None else _keypoint_init(cfg, device)
+        query_fn = keypoint_query(sp, sift=sift, track_num=_get(cfg, "train.track_num", 512))
+    mp = _get(cfg, "mixed_precision", "no")
+    stream = PoseStream(model, window=window, stride=int(_get(cfg, "stream.stride", 1)),
+                        capacity=_get(cfg, "stream.capacity", None), query_fn=query_fn,
+                        precision=torch.bfloat16 if mp == "bf16" else torch.float32)
+    logger = CsvLogger(csv_path, STREAM_FIELDS)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    hops = 0
+    for frame in frames_iter:
+        up = torch.as_tensor(frame)[None].to(device)
+        e0.record()
+        results = stream.push(crop_resize_normalize(up, box, (size, size))[0], query_points=query_points)
+        e1.record()
+        for r in results:
+            enc = r.pred_pose_enc[-1].tolist()  # (synchronises: the events are complete after it)
+            logger.log(dict(zip(STREAM_FIELDS, [r.frame_index, r.frame_index + window - 1] + enc + [e0.elapsed_time(e1)])))
+            hops += 1
+    return hops
+
+
+# ------------------------------------------------------------------------------------------------
 class CsvLogger:
     """abl_ours.py:9-22: header written once when the file is new, one DictWriter row per log()."""
 

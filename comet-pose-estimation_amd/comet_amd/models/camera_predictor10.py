@@ -159,15 +159,22 @@ class CameraPredictor(nn.Module):
         return t
 
     # ------------------------------------------------------------------------------------
-    def get_2D_image_features(self, reshaped_image, batch_size):
-        """camera_predictor10.py:622-687 -> (rgb_feat [B, S, C], B, S, C)."""
-        tok = self.backbone(reshaped_image, is_training=True, down_size=self.down_size)["x_norm_patchtokens"]
+    def frame_tokens(self, images):
+        """The per-frame head of get_2D_image_features: images [BS, 3, H, W] -> [BS, P, C] (backbone,
+        input_transform, non-affine LN, + 2-D sincos). Nothing here mixes frames."""
+        tok = self.backbone(images, is_training=True, down_size=self.down_size)["x_norm_patchtokens"]
         tok = self.input_transform(tok)
         tok = F.layer_norm(tok, eps=1e-6)
         BS, P, C = tok.shape
+        return F.add_rows(tok, self._table("2d", P, C, tok.device), P)
+
+    def get_2D_image_features(self, reshaped_image, batch_size, tokens=None):
+        """camera_predictor10.py:622-687 -> (rgb_feat [B, S, C], B, S, C). tokens: frame_tokens of
+        these B*S frames computed earlier (reshaped_image is then unused)."""
+        tok = self.frame_tokens(reshaped_image) if tokens is None else tokens
+        BS, P, C = tok.shape
         B = batch_size
         S = BS // B
-        tok = F.add_rows(tok, self._table("2d", P, C, tok.device), P)
         tok = tok.reshape(B, S, P, C)
         tok = torch.cat([self.pose_token.expand(B, S, -1, -1), tok], dim=-2)
         P = P + 1
@@ -220,9 +227,10 @@ class CameraPredictor(nn.Module):
         return torch.cat([f0[:, 0:1], r], dim=1)
 
     def forward(self, reshaped_image, preliminary_cameras=None, iters=4, batch_size=None, rgb_feat_init=None,
-                gt_cameras=None, fmaps=None, pred_trajectories=None, track_confidence=None, debug=False):
+                gt_cameras=None, fmaps=None, pred_trajectories=None, track_confidence=None, debug=False,
+                tokens=None):
         if rgb_feat_init is None:
-            rgb_feat, B, S, C = self.get_2D_image_features(reshaped_image, batch_size)
+            rgb_feat, B, S, C = self.get_2D_image_features(reshaped_image, batch_size, tokens=tokens)
         else:
             rgb_feat = rgb_feat_init
             B, S, C = rgb_feat.shape

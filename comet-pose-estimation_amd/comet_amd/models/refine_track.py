@@ -14,6 +14,13 @@ from .. import functional as F
 from .. import ops
 
 
+def refine_frame_input(images):
+    """What refine_track needs of each frame, computable one frame at a time (comet_amd.stream keeps
+    it in its ring): comet_patch_gather reads the f32 NCHW frames directly, so this is the frames
+    themselves, dense. images [..., 3, H, W] -> the same shape."""
+    return images.float().contiguous()
+
+
 @torch.no_grad()
 def refine_track(images, fine_fnet, fine_tracker, coarse_pred, pradius=15, sradius=2, compute_score=False,
                  fine_iters=6):

@@ -589,6 +589,32 @@ def cast_multi_f32_bf16(srcs, dsts):
     L.check(L.load().comet_cast_multi_f32_bf16(S, D, Z, n, stream()), "cast_multi")
 
 
+def ring_gather(pairs, slots, slots_host, max_blocks=0):
+    """For every (ring [capacity, ...], window [T, ...]) pair: window[j] = ring[slots[j]], all pairs
+    (at most 4) in one launch. slots: int32 [T] on the device; slots_host: the same T values on the
+    host (a ctypes int32 array), range-checked by the library before it launches."""
+    n, T = len(pairs), len(slots_host)
+    if n == 0:
+        return
+    cap = pairs[0][0].shape[0]
+    R = (L.RingTensor * n)()
+    for r, (ring, win) in zip(R, pairs):
+        _req_cuda(ring, win)
+        if (ring.dtype != win.dtype or ring.shape[0] != cap or win.shape[0] != T or ring.shape[1:] != win.shape[1:]
+                or not ring.is_contiguous() or not win.is_contiguous()):
+            raise L.CometHipError("ring_gather: ring [capacity, ...] and window [T, ...] must be dense, of one dtype "
+                                  "and slot shape, and every ring of one capacity")
+        r.src, r.dst, r.slot_bytes = ring.data_ptr(), win.data_ptr(), ring[0].numel() * ring.element_size()
+    if slots.dtype != torch.int32 or slots.numel() != T or not slots.is_contiguous():
+        raise L.CometHipError("ring_gather: slots must be a dense int32 [T] device tensor")
+    _req_cuda(slots)
+    e0 = PROF.start()
+    L.check(L.load().comet_ring_gather(R, n, _p(slots), ctypes.addressof(slots_host), T, cap, max_blocks, stream()),
+            "ring_gather")
+    if e0 is not None:
+        PROF.stop(e0, "comet_ring_gather", 0.0, float(2 * T * sum(r.slot_bytes for r in R)))
+
+
 def resize_bilinear_pool(x, oh, ow):
     """NHWC x [n, h, w, c] -> (y [n, oh, ow, c] bilinear, align_corners=True; its 2 x 2 average
     pool [n, oh // 2, ow // 2, c]) in one kernel: resize_bilinear + avgpool2_nhwc bit for bit."""

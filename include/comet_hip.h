@@ -505,6 +505,26 @@ int comet_sift_detect(const float* gauss, int B, int n_layers, int h, int w, int
                       int* count, int* overflow, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Online inference (comet_amd/stream.py, DESIGN.md "Online / streaming inference"): the per-frame
+ * tensors of the newest `capacity` frames are kept in device rings of equal-sized slots.
+ * comet_ring_gather: for each of n_tensors (1..COMET_RING_MAX_TENSORS) rings,
+ *   dst[j*slot_bytes : (j+1)*slot_bytes] = src[slots[j]*slot_bytes : ...] for j in [0, T), all rings
+ *   in ONE launch (16-B vector loads, streaming stores, a grid-stride loop over 16 KiB tiles sized
+ *   to the CU count). `slots` is the window's slot table on the device (int32 [T]); `slots_host`
+ *   holds the same T values on the host and is range-checked against `capacity` before the launch
+ *   (the kernel skips a slot outside [0, capacity) instead of reading it). slot_bytes must be a
+ *   multiple of 16 and src / dst 16-B aligned. max_blocks: 0 = 4 workgroups per CU, > 0 caps the
+ *   grid (tests: several grid passes at small sizes). */
+#define COMET_RING_MAX_TENSORS 4
+typedef struct CometRingTensor {
+  const void* src;     /* ring: capacity slots of slot_bytes */
+  void* dst;           /* window: T slots of slot_bytes, contiguous */
+  int64_t slot_bytes;
+} CometRingTensor;
+int comet_ring_gather(const CometRingTensor* tensors, int n_tensors, const int32_t* slots,
+                      const int32_t* slots_host, int T, int capacity, int max_blocks, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Debug support (bounds asserts and a NaN / Inf check mode).
  * comet_count_nonfinite: adds the number of NaN / Inf elements of x (n elements, dtype) to
  *   *count (an int32 on the device; no host sync). Used by comet_amd.debug's finite-check hooks.

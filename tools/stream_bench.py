@@ -1,0 +1,95 @@
+"""Online inference: time per hop of comet_amd.stream.PoseStream against the closed-window call.
+
+    python tools/stream_bench.py [--frames 16 --image 512 --tracks 512 --hops 32 --warmup 4]
+
+Synthetic frames of the SURVEY 8(d) recipe (N(0,1) frames, U[0, S-1] query points), random-init
+weights, bf16, stride 1. After the warm-up hops, `--hops` hops each of
+  (a) stream   one push of the newest frame: its per-frame stages, the ring store, the gather, the
+               cross-frame part of the model;
+  (b) closed   the same windows through model(window, training=False, tracks=...), what a caller
+               without the stream runs per hop;
+  (c) gather   the comet_ring_gather launch alone (with the bytes it moves: achieved bandwidth).
+Each hop is timed with device events; the figures are medians. (a) and (b) alternate hop by hop, so
+both see the same machine state. One JSON line. Needs a GPU (no fallback)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+GATHER_REPS = 20
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "comet-pose-estimation_amd"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=16, help="window length T")
+    ap.add_argument("--image", type=int, default=512)
+    ap.add_argument("--tracks", type=int, default=512)
+    ap.add_argument("--hops", type=int, default=32)
+    ap.add_argument("--warmup", type=int, default=4)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        print("stream_bench: no GPU", file=sys.stderr)
+        return 2
+    from comet_amd import functional as F
+    from comet_amd.config import instantiate, load_config
+    from comet_amd.stream import PoseStream
+    T, S, N = args.frames, args.image, args.tracks
+    dev = torch.device("cuda", 0)
+    cfg = load_config()
+    torch.manual_seed(0)
+    model = instantiate(cfg.MODEL, _recursive_=False, cfg=cfg).to(dev).eval()
+    g = torch.Generator(device=dev).manual_seed(1)
+    total = T + args.warmup + args.hops - 1
+    frames = torch.randn(total, 3, S, S, device=dev, generator=g)
+    q = torch.rand(N, 2, device=dev, generator=g) * (S - 1)
+    tracks = q[None, None].expand(1, T, N, 2)
+    stream = PoseStream(model, window=T, stride=1, precision=torch.bfloat16)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    def closed(k):
+        with F.precision(torch.bfloat16):
+            return model(frames[None, k:k + T], training=False, tracks=tracks)
+
+    stream.push(frames[:T - 1], query_points=q)
+    ta, tb, tc, err = [], [], [], 0.0
+    for k in range(args.warmup + args.hops):
+        ms_a, res = timed(lambda: stream.push(frames[k + T - 1], query_points=q))
+        ms_b, ref = timed(lambda: closed(k))
+        assert len(res) == 1 and res[0].frame_index == k
+        ms_c, _ = timed(lambda: [stream._gather(k % stream.sched.capacity) for _ in range(GATHER_REPS)])
+        ms_c /= GATHER_REPS
+        if k >= args.warmup:
+            ta.append(ms_a)
+            tb.append(ms_b)
+            tc.append(ms_c)
+            err = max(err, float((res[0].pred_pose_enc - ref["pred_pose_enc"]).abs().max()))
+    nbytes = sum(2 * w.numel() * w.element_size() for w in stream._wins if w is not None)
+    a, b, c = statistics.median(ta), statistics.median(tb), statistics.median(tc)
+    print(json.dumps({
+        "metric": f"ms per hop, online COMET inference, T={T} {S}^2 N={N}, bf16, stride 1",
+        "stream_ms": round(a, 3), "closed_window_ms": round(b, 3), "gather_ms": round(c, 4),
+        "closed_over_stream": round(b / a, 3), "stream_hops_per_s": round(1e3 / a, 2),
+        "gather_bytes_read_plus_written": nbytes, "gather_GBps": round(nbytes / (c * 1e-3) / 1e9, 1),
+        "gather_timing": f"device events around {GATHER_REPS} back-to-back launches / {GATHER_REPS}, median over the hops",
+        "hops": args.hops, "warmup": args.warmup, "min_stream_ms": round(min(ta), 3), "min_closed_ms": round(min(tb), 3),
+        "max_abs_pose_enc_diff_stream_vs_closed": err,
+        "slot_bytes": {n: (w[0].numel() * w.element_size() if w is not None else 0)
+                       for n, w in zip(("fmaps", "frames", "tokens"), stream._wins)},
+        "data": "synthetic (N(0,1) frames, U[0,S-1] query points); random-init weights"}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main() or 0)
