@@ -182,6 +182,7 @@ SIGNATURES = {
     "comet_track_score": (_INT, [_INT, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, _INT, c_i64, _INT, _INT, _INT, c_vp]),
     "comet_dino_prep": (_INT, [_INT, c_vp, c_vp, c_i64, _INT, _INT, _INT, _INT, c_i64, c_vp, c_vp, c_vp]),
     "comet_ring_gather": (_INT, [ctypes.POINTER(RingTensor), _INT, c_vp, c_vp, _INT, _INT, _INT, c_vp]),
+    "comet_ring_scatter": (_INT, [ctypes.POINTER(RingTensor), _INT, c_vp, c_vp, _INT, _INT, _INT, c_vp]),
 }
 
 _lib = None

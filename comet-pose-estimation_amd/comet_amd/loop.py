@@ -649,6 +649,68 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
     return hops
 
 
+def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_points=None, device="cuda"):
+    """stream_eval for several sequences at a time (opt-in: cfg.stream.enable). `sequences` is an
+    iterable of (name, frames_iter, box), each as stream_eval takes them; cfg.stream.streams
+    (default 4) streams of one comet_amd.stream.StreamPool run side by side. Every free stream takes
+    the next sequence (reset(stream), then its frames); one push carries one frame of every running
+    sequence, and when a sequence ends the pool goes on with the streams that remain. One CSV per
+    sequence, csv_dir/<name>.csv, with the rows stream_eval writes; hop_ms is the time of the push
+    that completed the hop (the frames of all running streams and all hops due in it), from device
+    events. -> {name: number of hops}."""
+    from .data import crop_resize_normalize
+    from .stream import StreamPool, keypoint_query
+    if not _get(cfg, "stream.enable", False):
+        raise ValueError("stream_eval_pool is opt-in: set cfg.stream.enable")
+    model.eval()
+    window = int(_get(cfg, "stream.window", _get(cfg, "seqlen", 16)))
+    size = int(_get(cfg, "train.img_size", 512))
+    S = int(_get(cfg, "stream.streams", 4))
+    query_fn = None
+    if query_points is None:
+        sp = sp if sp is not None else _keypoint_init(cfg, device)
+        query_fn = keypoint_query(sp, sift=sift, track_num=_get(cfg, "train.track_num", 512))
+    mp = _get(cfg, "mixed_precision", "no")
+    pool = StreamPool(model, streams=S, window=window, stride=int(_get(cfg, "stream.stride", 1)),
+                      capacity=_get(cfg, "stream.capacity", None), query_fn=query_fn,
+                      precision=torch.bfloat16 if mp == "bf16" else torch.float32)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    seqs = iter(sequences)
+    running = {}  # stream id -> (name, frame iterator, box, logger)
+    hops = {}
+
+    def next_frame(sid):
+        """The next frame of stream sid's sequence, moving on to the next sequence when it ends."""
+        while True:
+            if sid not in running:
+                nxt = next(seqs, None)
+                if nxt is None:
+                    return None
+                name, frames_iter, box = nxt
+                pool.reset(sid)
+                running[sid] = (name, iter(frames_iter), box, CsvLogger(os.path.join(csv_dir, f"{name}.csv"), STREAM_FIELDS))
+                hops[name] = 0
+            frame = next(running[sid][1], None)
+            if frame is not None:
+                return frame
+            del running[sid]
+
+    while True:
+        new = [(sid, frame) for sid in range(S) for frame in [next_frame(sid)] if frame is not None]
+        if not new:
+            return hops
+        ups = [torch.as_tensor(frame)[None].to(device) for _, frame in new]
+        e0.record()
+        frames = torch.cat([crop_resize_normalize(up, running[sid][2], (size, size)) for (sid, _), up in zip(new, ups)])
+        results = pool.push(frames, streams=[sid for sid, _ in new], query_points=query_points)
+        e1.record()
+        for sid, r in results:
+            enc = r.pred_pose_enc[-1].tolist()  # (synchronises: the events are complete after it)
+            name, logger = running[sid][0], running[sid][3]
+            logger.log(dict(zip(STREAM_FIELDS, [r.frame_index, r.frame_index + window - 1] + enc + [e0.elapsed_time(e1)])))
+            hops[name] += 1
+
+
 # ------------------------------------------------------------------------------------------------
 class CsvLogger:
     """abl_ours.py:9-22: header written once when the file is new, one DictWriter row per log()."""

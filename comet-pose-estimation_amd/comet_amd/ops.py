@@ -615,6 +615,33 @@ def ring_gather(pairs, slots, slots_host, max_blocks=0):
         PROF.stop(e0, "comet_ring_gather", 0.0, float(2 * T * sum(r.slot_bytes for r in R)))
 
 
+def ring_scatter(pairs, slots, slots_host, max_blocks=0):
+    """The inverse of ring_gather. For every (src [k, ...], ring [capacity, ...]) pair:
+    ring[slots[j]] = src[j], all pairs (at most 4) in one launch. slots: int32 [k] on the device;
+    slots_host: the same k values on the host (a ctypes int32 array); the library checks their range
+    and that no two are equal before it launches."""
+    n, k = len(pairs), len(slots_host)
+    if n == 0:
+        return
+    cap = pairs[0][1].shape[0]
+    R = (L.RingTensor * n)()
+    for r, (src, ring) in zip(R, pairs):
+        _req_cuda(src, ring)
+        if (ring.dtype != src.dtype or ring.device != src.device or ring.shape[0] != cap or src.shape[0] != k
+                or ring.shape[1:] != src.shape[1:] or not ring.is_contiguous() or not src.is_contiguous()):
+            raise L.CometHipError("ring_scatter: src [k, ...] and ring [capacity, ...] must be dense, of one dtype, "
+                                  "device and slot shape, and every ring of one capacity")
+        r.src, r.dst, r.slot_bytes = src.data_ptr(), ring.data_ptr(), ring[0].numel() * ring.element_size()
+    if slots.dtype != torch.int32 or slots.numel() != k or not slots.is_contiguous():
+        raise L.CometHipError("ring_scatter: slots must be a dense int32 [k] device tensor")
+    _req_cuda(slots)
+    e0 = PROF.start()
+    L.check(L.load().comet_ring_scatter(R, n, _p(slots), ctypes.addressof(slots_host), k, cap, max_blocks, stream()),
+            "ring_scatter")
+    if e0 is not None:
+        PROF.stop(e0, "comet_ring_scatter", 0.0, float(2 * k * sum(r.slot_bytes for r in R)))
+
+
 def resize_bilinear_pool(x, oh, ow):
     """NHWC x [n, h, w, c] -> (y [n, oh, ow, c] bilinear, align_corners=True; its 2 x 2 average
     pool [n, oh // 2, ow // 2, c]) in one kernel: resize_bilinear + avgpool2_nhwc bit for bit."""

@@ -10,6 +10,9 @@ them once per frame, keeps their outputs in device rings, and for every hop gath
 
   RingSchedule   the slot / hop arithmetic, host only (no tensors)
   PoseStream     push(frame | frames) -> one StreamResult per completed hop
+  PoolSchedule   the same arithmetic for S streams over pooled rings, host only
+  StreamPool     S streams on one model: push(one frame per stream) runs the per-frame stages, the
+                 ring store (comet_ring_scatter) and the hops that fall due as one batch each
   keypoint_query query_fn from the SuperPoint / SIFT detectors of comet_amd.keypoints
 """
 import ctypes
@@ -92,6 +95,36 @@ def _model_precision(model):
     cfg = getattr(model, "cfg", None)
     mp = cfg.get("mixed_precision", "no") if cfg is not None and hasattr(cfg, "get") else "no"
     return torch.bfloat16 if mp == "bf16" else torch.float32
+
+
+def _anchor_ref(anchor, dev):
+    """Anchor -> ((R [4] f32, T_uvz [3] f32) the first hop is decoded against, ratio as a float64
+    device scalar)."""
+    ref = (torch.as_tensor(anchor.R, dtype=torch.float32).to(dev).reshape(4),
+           torch.as_tensor(anchor.T_uvz, dtype=torch.float32).to(dev).reshape(3))
+    return ref, torch.as_tensor(anchor.ratio, dtype=torch.float64).reshape(-1)[0].to(dev)
+
+
+def _decode_chained(a, ref, ratio, s, enc, T):
+    """One window's absolute poses: enc [T, 7] decoded against ref = (R [4], T_uvz [3]) of its first
+    frame -> (R [T, 4], T [T, 3] float64, the next window's ref). s: the position in this window of
+    the next window's first frame (RingSchedule.chain_index)."""
+    from .models.utils import INTRINSICS
+    Rref, uvz = ref
+    intr = INTRINSICS[a.dataset]
+    R, Tx = ops.pose_decode(enc, Rref.expand(T, 4).contiguous(), uvz.expand(T, 3).contiguous(), a.ratio, intr, 1, T)
+    # the next window's reference: this window's frame `stride`, its (u, v, z) in the codec's f32
+    e = enc[s].double()
+    u0 = uvz.double()
+    nxt = torch.stack([u0[0] + e[0] / ratio * 128.0, u0[1] + e[1] / ratio * 128.0,
+                       u0[2] * (e[2] / ratio + 1.0)]).float()
+    ref = (R[s].clone(), nxt)
+    # report frame `stride` as the next window will see it (its first frame decodes to exactly this)
+    ident = torch.zeros(1, 7, device=enc.device)
+    ident[0, 3] = 1.0
+    Rs, Ts = ops.pose_decode(ident, ref[0][None], nxt[None], a.ratio, intr, 1, 1)
+    R[s], Tx[s] = Rs[0], Ts[0]
+    return R, Tx, ref
 
 
 class PoseStream:
@@ -179,24 +212,7 @@ class PoseStream:
 
     # -- hops -------------------------------------------------------------------------------------
     def _decode(self, enc, T):
-        from .models.utils import INTRINSICS
-        a = self.anchor
-        Rref, uvz = self._ref
-        intr = INTRINSICS[a.dataset]
-        R, Tx = ops.pose_decode(enc, Rref.expand(T, 4).contiguous(), uvz.expand(T, 3).contiguous(), a.ratio, intr, 1, T)
-        # the next window's reference: this window's frame `stride`, its (u, v, z) in the codec's f32
-        s = self.sched.chain_index()
-        ratio = self._ratio
-        e = enc[s].double()
-        u0 = uvz.double()
-        nxt = torch.stack([u0[0] + e[0] / ratio * 128.0, u0[1] + e[1] / ratio * 128.0,
-                           u0[2] * (e[2] / ratio + 1.0)]).float()
-        self._ref = (R[s].clone(), nxt)
-        # report frame `stride` as the next window will see it (its first frame decodes to exactly this)
-        ident = torch.zeros(1, 7, device=enc.device)
-        ident[0, 3] = 1.0
-        Rs, Ts = ops.pose_decode(ident, self._ref[0][None], nxt[None], a.ratio, intr, 1, 1)
-        R[s], Tx[s] = Rs[0], Ts[0]
+        R, Tx, self._ref = _decode_chained(self.anchor, self._ref, self._ratio, self.sched.chain_index(), enc, T)
         return R, Tx
 
     def _hop(self, hop, query_points):
@@ -236,16 +252,255 @@ class PoseStream:
                 self._allocate(per, frames.device)
                 self._hw = hw
                 if self.anchor is not None:
-                    a, dev = self.anchor, frames.device
-                    self._ref = (torch.as_tensor(a.R, dtype=torch.float32).to(dev).reshape(4),
-                                 torch.as_tensor(a.T_uvz, dtype=torch.float32).to(dev).reshape(3))
-                    self._ratio = torch.as_tensor(a.ratio, dtype=torch.float64).reshape(-1)[0].to(dev)
+                    self._ref, self._ratio = _anchor_ref(self.anchor, frames.device)
             for i in range(frames.shape[0]):
                 slot, hop = self.sched.push()
                 self._store(per, i, slot)
                 if hop is not None:
                     results.append(self._hop(hop, query_points))
         return results
+
+
+class PoolSchedule:
+    """The host-only arithmetic of a StreamPool (no tensors): `streams` RingSchedule objects over
+    pooled rings of streams * capacity slots. Frame f of stream s lives in slot
+    s * capacity + f % capacity, so slots of different streams never coincide; a stream's hops fall
+    due exactly where its own RingSchedule says."""
+
+    def __init__(self, streams, window, stride=1, capacity=None):
+        if streams < 1:
+            raise ValueError(f"a pool needs at least 1 stream, got {streams}")
+        self.streams = int(streams)
+        self.scheds = [RingSchedule(window, stride, capacity) for _ in range(self.streams)]
+        s0 = self.scheds[0]
+        self.window, self.stride, self.capacity = s0.window, s0.stride, s0.capacity
+
+    def reset(self, stream=None):
+        for s in (range(self.streams) if stream is None else self.ids(1, [stream])):
+            self.scheds[s].reset()
+
+    def ids(self, k, streams=None):
+        """The stream ids of a push of k frames: `streams` (k distinct known ids), default
+        range(streams), which needs k == streams."""
+        if streams is None:
+            if k != self.streams:
+                raise ValueError(f"push of {k} frames into a pool of {self.streams} streams: pass `streams`, the id "
+                                 "of each frame's stream")
+            return list(range(self.streams))
+        ids = [int(s) for s in streams]
+        if len(ids) != k:
+            raise ValueError(f"{k} frames for {len(ids)} stream ids")
+        for s in ids:
+            if not 0 <= s < self.streams:
+                raise ValueError(f"unknown stream {s}: the pool has streams 0 .. {self.streams - 1}")
+        if len(set(ids)) != len(ids):
+            raise ValueError(f"a stream takes one frame per push, got the ids {ids}")
+        return ids
+
+    def slot(self, stream, frame_index):
+        return stream * self.capacity + self.scheds[stream].slot(frame_index)
+
+    def window_slots(self, stream, head):
+        """RingSchedule.window_slots(head) of the stream, shifted by stream * capacity."""
+        return [stream * self.capacity + s for s in self.scheds[stream].window_slots(head)]
+
+    def due(self, ids):
+        """The streams among `ids` whose next frame completes a hop (nothing is advanced)."""
+        out = []
+        for s in ids:
+            first = self.scheds[s].frames_seen + 1 - self.window
+            if first >= 0 and first % self.stride == 0:
+                out.append(s)
+        return sorted(out)
+
+    def push(self, ids):
+        """Account for one new frame of every stream in `ids` -> (the absolute slot of each frame, in
+        the order of `ids`; [(stream, Hop)] of the hops this completes, ordered by stream id)."""
+        slots, hops = [], []
+        for s in ids:
+            slot, hop = self.scheds[s].push()
+            slots.append(s * self.capacity + slot)
+            if hop is not None:
+                hops.append((s, hop))
+        return slots, sorted(hops)
+
+    def table(self, hops):
+        """The concatenated slot table of the windows of `hops` [(stream, Hop)]: len(hops) * window
+        absolute slots, a valid comet_ring_gather table over the pooled ring."""
+        return [s for stream, hop in hops for s in self.window_slots(stream, hop.head)]
+
+    @staticmethod
+    def group(counts):
+        """Due hops with the query counts `counts` (one per hop, hops ordered by stream id) ->
+        [(N, [positions of the hops with N query points, ascending])], in the order each N first
+        appears: every group is one batched call."""
+        groups = {}
+        for i, n in enumerate(counts):
+            groups.setdefault(int(n), []).append(i)
+        return list(groups.items())
+
+
+class StreamPool:
+    """Several PoseStream-like streams that share one model and batch their work.
+
+        pool = StreamPool(model, streams=S, window=16, query_fn=keypoint_query(sp))
+        for frames in cameras:                       # [S, 3, H, W], one new frame per stream
+            for sid, r in pool.push(frames):         # r: StreamResult, as PoseStream returns
+                use(sid, r.frame_index, r.pred_pose_enc)
+
+    One push takes at most one frame per stream (`streams`: the k distinct ids of the k frames;
+    default all S in order). The k frames go through the per-frame stages as one batch
+    (model.frame_stages), one comet_ring_scatter launch stores their outputs in pooled rings
+    [S * capacity, ...] (PoolSchedule: stream s, frame f -> slot s * capacity + f % capacity), and
+    the n hops that fall due in the push are gathered by one comet_ring_gather launch and run as one
+    model.forward_all with B = n. Streams need not be in phase: one can be absent from a push, start
+    later, or be restarted with reset(stream).
+
+    Query points of a due hop: `query_points` of the push ([N, 2] shared by all streams, or a dict
+    by stream id), else query_fn(first frame of the window). Hops whose query counts differ
+    (filter_and_pad returns between min_required and track_num points) are grouped by N, one
+    batched call per group. anchors: a dict or list giving every stream the 5-tuple PoseStream
+    takes; each stream chains its absolute poses as PoseStream does (decoded per stream by the same
+    code, so for the same pred_pose_enc the same bits).
+
+    push() -> [(stream id, StreamResult)] ordered by stream id. The tensors of a result are views
+    of the batched outputs. The model is used as is (its eval / train mode included)."""
+
+    _TABLES_MAX = 1024  # cached device slot tables (periodic in capacity for streams in phase)
+
+    def __init__(self, model, streams, window, stride=1, capacity=None, query_fn=None, anchors=None, precision=None):
+        self.model = model
+        self.sched = PoolSchedule(streams, window, stride, capacity)
+        self.query_fn = query_fn
+        self.precision = precision if precision is not None else _model_precision(model)
+        self.anchors = None
+        if anchors is not None:
+            self.sched.scheds[0].chain_index()  # raises unless stride < window
+            items = anchors.items() if isinstance(anchors, dict) else enumerate(anchors)
+            self.anchors = {int(s): Anchor(*a) for s, a in items}
+            if sorted(self.anchors) != list(range(self.sched.streams)):
+                raise ValueError(f"anchors must name every stream 0 .. {self.sched.streams - 1}, got "
+                                 f"{sorted(self.anchors)}")
+        self._ratios = {}
+        self.reset()
+
+    def reset(self, stream=None):
+        """reset(s): stream s forgets its frames (its next frame is frame 0, at its anchor); the
+        other streams go on. reset(): every stream, and the rings are dropped (a new frame size may
+        follow)."""
+        self.sched.reset(stream)
+        if stream is None:
+            self._rings = self._wins = self._hw = self._dev = None
+            self._tables = {}
+            self._refs = {}
+        else:
+            self._refs.pop(int(stream), None)
+
+    # -- rings ------------------------------------------------------------------------------------
+    def _allocate(self, per, dev):
+        S, cap, T = self.sched.streams, self.sched.capacity, self.sched.window
+        self._rings, self._wins = [], []
+        for t in per:
+            if t is None:
+                self._rings.append(None)
+                self._wins.append(None)
+                continue
+            slot = t.shape[1:]
+            if (slot.numel() * t.element_size()) % 16 != 0:
+                raise ValueError(f"frame size not supported by the ring: a slot of {tuple(slot)} {t.dtype} is no "
+                                 "multiple of 16 bytes")
+            self._rings.append(torch.empty(S * cap, *slot, device=dev, dtype=t.dtype))
+            self._wins.append(torch.empty(S * T, *slot, device=dev, dtype=t.dtype))
+        self._dev = dev
+
+    def _table(self, values):
+        """A slot table on the device (int32) and on the host (ctypes), cached by its values."""
+        key = tuple(values)
+        hit = self._tables.get(key)
+        if hit is None:
+            if len(self._tables) >= self._TABLES_MAX:
+                self._tables.clear()
+            hit = (torch.tensor(key, dtype=torch.int32, device=self._dev), (ctypes.c_int32 * len(key))(*key))
+            self._tables[key] = hit
+        return hit
+
+    def _query(self, sid, hop, query_points):
+        q = query_points.get(sid) if isinstance(query_points, dict) else query_points
+        if q is None:
+            q = self.query_fn(self._rings[1][self.sched.slot(sid, hop.frame_index)])
+        return q.to(self._dev, torch.float32)
+
+    def _decode(self, sid, enc, T):
+        a = self.anchors[sid]
+        if sid not in self._refs:
+            self._refs[sid], self._ratios[sid] = _anchor_ref(a, enc.device)
+        R, Tx, self._refs[sid] = _decode_chained(a, self._refs[sid], self._ratios[sid],
+                                                 self.sched.scheds[sid].chain_index(), enc, T)
+        return R, Tx
+
+    # -- hops -------------------------------------------------------------------------------------
+    def _hops(self, hops, qs, pos):
+        """The hops hops[i], i in pos (all with N query points) as one batched call ->
+        [(stream, StreamResult)] in the order of pos."""
+        from .models.E2Epose2 import FrameCache
+        T, n = self.sched.window, len(pos)
+        table, table_host = self._table(self.sched.table([hops[i] for i in pos]))
+        wins = [None if w is None else w[:n * T] for w in self._wins]
+        ops.ring_gather([(r, w) for r, w in zip(self._rings, wins) if r is not None], table, table_host)
+        fm, fr, tok = wins
+        cache = FrameCache(fmaps=None if fm is None else fm.view(n, T, *fm.shape[1:]),
+                           refine_frames=fr.view(n, T, *fr.shape[1:]), tokens=tok)
+        tracks = torch.stack([qs[i] for i in pos])[:, None].expand(n, T, -1, 2)
+        # (with a frame_cache the model reads only the shape of its image argument)
+        out = self.model.forward_all(cache.refine_frames, training=False, tracks=tracks, frame_cache=cache)
+        enc = out["pred_pose_enc"]  # [n * T, 7]
+        tr = out.get("pred_tracks")
+        sc = out.get("_track_predictions", {}).get("pred_score")
+        results = []
+        for b, i in enumerate(pos):
+            sid, hop = hops[i]
+            e = enc[b * T:(b + 1) * T]
+            R = Tx = None
+            if self.anchors is not None:
+                R, Tx = self._decode(sid, e, T)
+            results.append((sid, StreamResult(hop.frame_index, e, None if tr is None else tr[b],
+                                              None if sc is None else sc[b], R, Tx)))
+        return results
+
+    @torch.no_grad()
+    def push(self, frames, streams=None, query_points=None):
+        """frames [k, 3, H, W] f32 on the model's device, one per stream of `streams` (k distinct
+        ids; default: all streams in order) -> [(stream id, StreamResult)] of the hops the frames
+        complete, ordered by stream id (often empty). Bad arguments raise ValueError before anything
+        is launched."""
+        if frames.dim() != 4 or frames.shape[1] != 3:
+            raise ValueError(f"push takes [k, 3, H, W] frames, got {tuple(frames.shape)}")
+        ids = self.sched.ids(frames.shape[0], streams)
+        hw = tuple(frames.shape[-2:])
+        if self._hw is not None and hw != self._hw:
+            raise ValueError(f"frame size changed from {self._hw} to {hw}; reset() starts new streams")
+        if self.query_fn is None:
+            if query_points is None:
+                raise ValueError("no query source: pass query_points to push() or query_fn to StreamPool")
+            if isinstance(query_points, dict):
+                missing = [s for s in self.sched.due(ids) if query_points.get(s) is None]
+                if missing:
+                    raise ValueError(f"no query source for the streams {missing}, whose hop is due in this push")
+        results = []
+        with F.precision(self.precision):
+            per = PoseStream._per_frame(self.model.frame_stages(frames.float()))
+            if self._rings is None:
+                self._allocate(per, frames.device)
+                self._hw = hw
+            slots, hops = self.sched.push(ids)
+            slot_table, slot_host = self._table(slots)
+            ops.ring_scatter([(t.contiguous(), r) for t, r in zip(per, self._rings) if r is not None],
+                             slot_table, slot_host)
+            if hops:
+                qs = [self._query(sid, hop, query_points) for sid, hop in hops]
+                for _, pos in self.sched.group([q.shape[0] for q in qs]):
+                    results += self._hops(hops, qs, pos)
+        return sorted(results, key=lambda r: r[0])
 
 
 def keypoint_query(sp, sift=None, mask_fn=None, track_num=512, min_required=256):

@@ -523,6 +523,15 @@ typedef struct CometRingTensor {
 } CometRingTensor;
 int comet_ring_gather(const CometRingTensor* tensors, int n_tensors, const int32_t* slots,
                       const int32_t* slots_host, int T, int capacity, int max_blocks, void* stream);
+/* comet_ring_scatter: the inverse, for the k new frames of a push (comet_amd.stream.StreamPool: one
+ *   frame per stream). Here `src` is a contiguous block of k rows of slot_bytes and `dst` the ring:
+ *   dst[slots[j]*slot_bytes : ...] = src[j*slot_bytes : (j+1)*slot_bytes] for j in [0, k), all rings
+ *   in ONE launch (same tiling and grid; plain stores: the gather of the same push reads the slots
+ *   again). slots / slots_host as above; besides the range check the k host values must be distinct
+ *   (two rows for one slot would race). The kernel skips a slot outside [0, capacity) instead of
+ *   writing it. */
+int comet_ring_scatter(const CometRingTensor* tensors, int n_tensors, const int32_t* slots,
+                       const int32_t* slots_host, int k, int capacity, int max_blocks, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Debug support (bounds asserts and a NaN / Inf check mode).

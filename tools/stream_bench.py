@@ -1,6 +1,7 @@
 """Online inference: time per hop of comet_amd.stream.PoseStream against the closed-window call.
 
     python tools/stream_bench.py [--frames 16 --image 512 --tracks 512 --hops 32 --warmup 4]
+    python tools/stream_bench.py --streams 1,2,4,8      (the stream pool, see below)
 
 Synthetic frames of the SURVEY 8(d) recipe (N(0,1) frames, U[0, S-1] query points), random-init
 weights, bf16, stride 1. After the warm-up hops, `--hops` hops each of
@@ -10,7 +11,17 @@ weights, bf16, stride 1. After the warm-up hops, `--hops` hops each of
                without the stream runs per hop;
   (c) gather   the comet_ring_gather launch alone (with the bytes it moves: achieved bandwidth).
 Each hop is timed with device events; the figures are medians. (a) and (b) alternate hop by hop, so
-both see the same machine state. One JSON line. Needs a GPU (no fallback)."""
+both see the same machine state. One JSON line. Needs a GPU (no fallback).
+
+--streams S[,S...]: comet_amd.stream.StreamPool against separate streams instead, one JSON line per
+S. Every stream has its own frames; all are in phase, so every timed push completes S hops. Per push
+  (a) pool      one StreamPool.push of S frames: the per-frame stages at batch S, one
+                comet_ring_scatter, one comet_ring_gather, the cross-frame part at B = S;
+  (b) separate  S independent PoseStream objects pushed one after another with the same frames (what
+                a caller without the pool runs);
+  (c) scatter   the comet_ring_scatter launch of a push alone, into a scratch ring (with the bytes it
+                moves: achieved bandwidth).
+(a) and (b) alternate push by push in one process; device events, medians and minima."""
 import argparse
 import json
 import os
@@ -24,6 +35,65 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "comet-pose-estimation_amd"))
 
 
+def _timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1), out
+
+
+def pool_bench(model, n_streams, args, dev):
+    from comet_amd import ops
+    from comet_amd.stream import PoseStream, StreamPool
+    T, S, N = args.frames, args.image, args.tracks
+    g = torch.Generator(device=dev).manual_seed(1)
+    total = T + args.warmup + args.hops - 1
+    frames = torch.randn(total, n_streams, 3, S, S, device=dev, generator=g)  # frames[f]: one push
+    q = torch.rand(N, 2, device=dev, generator=g) * (S - 1)
+    pool = StreamPool(model, streams=n_streams, window=T, stride=1, precision=torch.bfloat16)
+    singles = [PoseStream(model, window=T, stride=1, precision=torch.bfloat16) for _ in range(n_streams)]
+
+    def separate(f):
+        return [st.push(frames[f, s], query_points=q) for s, st in enumerate(singles)]
+
+    for f in range(T - 1):
+        assert pool.push(frames[f], query_points=q) == [] and not any(separate(f))
+    live = [(w, r) for w, r in zip(pool._wins, pool._rings) if r is not None]
+    srcs = [w[:n_streams] for w, _ in live]           # k = S rows of each cached kind
+    scratch = [torch.empty_like(r) for _, r in live]  # (the pool's own rings are left alone)
+    ta, tb, tc, err = [], [], [], 0.0
+    for k in range(args.warmup + args.hops):
+        f = k + T - 1
+        ms_a, res = _timed(lambda: pool.push(frames[f], query_points=q))
+        ms_b, ref = _timed(lambda: separate(f))
+        assert [s for s, _ in res] == list(range(n_streams)) and all(len(r) == 1 for r in ref)
+        slots = [pool.sched.slot(s, f) for s in range(n_streams)]
+        table, table_host = pool._table(slots)
+        ms_c, _ = _timed(lambda: [ops.ring_scatter(list(zip(srcs, scratch)), table, table_host) for _ in range(GATHER_REPS)])
+        if k >= args.warmup:
+            ta.append(ms_a)
+            tb.append(ms_b)
+            tc.append(ms_c / GATHER_REPS)
+            for (s, r), one in zip(res, ref):
+                assert r.frame_index == one[0].frame_index == k
+                err = max(err, float((r.pred_pose_enc - one[0].pred_pose_enc).abs().max()))
+    nbytes = 2 * n_streams * sum(r[0].numel() * r.element_size() for r in scratch)
+    a, b, c = statistics.median(ta), statistics.median(tb), statistics.median(tc)
+    print(json.dumps({
+        "metric": f"ms per push of {n_streams} streams (each push completes {n_streams} hops), online COMET inference, "
+                  f"T={T} {S}^2 N={N}, bf16, stride 1",
+        "streams": n_streams, "pool_ms": round(a, 3), "separate_ms": round(b, 3), "separate_over_pool": round(b / a, 3),
+        "pool_hops_per_s": round(n_streams * 1e3 / a, 2), "separate_hops_per_s": round(n_streams * 1e3 / b, 2),
+        "min_pool_ms": round(min(ta), 3), "min_separate_ms": round(min(tb), 3),
+        "scatter_ms": round(c, 4), "min_scatter_ms": round(min(tc), 4), "scatter_bytes_read_plus_written": nbytes,
+        "scatter_GBps": round(nbytes / (c * 1e-3) / 1e9, 1),
+        "scatter_timing": f"device events around {GATHER_REPS} back-to-back launches / {GATHER_REPS}, median over the pushes",
+        "pushes": args.hops, "warmup": args.warmup, "max_abs_pose_enc_diff_pool_vs_separate": err,
+        "data": "synthetic (N(0,1) frames, U[0,S-1] query points); random-init weights"}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16, help="window length T")
@@ -31,6 +101,8 @@ def main():
     ap.add_argument("--tracks", type=int, default=512)
     ap.add_argument("--hops", type=int, default=32)
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--streams", type=str, default=None,
+                    help="comma-separated stream counts: time StreamPool against that many separate PoseStream objects")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         print("stream_bench: no GPU", file=sys.stderr)
@@ -43,6 +115,10 @@ def main():
     cfg = load_config()
     torch.manual_seed(0)
     model = instantiate(cfg.MODEL, _recursive_=False, cfg=cfg).to(dev).eval()
+    if args.streams is not None:
+        for n_streams in [int(v) for v in args.streams.split(",")]:
+            pool_bench(model, n_streams, args, dev)
+        return 0
     g = torch.Generator(device=dev).manual_seed(1)
     total = T + args.warmup + args.hops - 1
     frames = torch.randn(total, 3, S, S, device=dev, generator=g)
