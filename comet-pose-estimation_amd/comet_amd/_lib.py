@@ -92,6 +92,7 @@ class RingTensor(ctypes.Structure):
 
 
 RING_MAX_TENSORS = 4  # COMET_RING_MAX_TENSORS
+FUSE_ROW = 20         # COMET_FUSE_ROW: doubles per accumulator row of comet_pose_fuse
 
 # (name, restype, argtypes); every exported symbol of include/comet_hip.h
 _F = ctypes.c_float
@@ -183,6 +184,9 @@ SIGNATURES = {
     "comet_dino_prep": (_INT, [_INT, c_vp, c_vp, c_i64, _INT, _INT, _INT, _INT, c_i64, c_vp, c_vp, c_vp]),
     "comet_ring_gather": (_INT, [ctypes.POINTER(RingTensor), _INT, c_vp, c_vp, _INT, _INT, _INT, c_vp]),
     "comet_ring_scatter": (_INT, [ctypes.POINTER(RingTensor), _INT, c_vp, c_vp, _INT, _INT, _INT, c_vp]),
+    "comet_pose_fuse": (_INT, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_double, c_vp,
+                               ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp,
+                               _INT, _INT, _INT, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

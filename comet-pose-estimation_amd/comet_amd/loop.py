@@ -607,9 +607,57 @@ def sequence_stream(seq_dir):
 
 
 STREAM_FIELDS = ("frame_index", "newest_frame", "du", "dv", "dd", "qw", "qx", "qy", "qz", "hop_ms")
+# cfg.stream.fuse: one row per frame whose fused pose is final, these columns after the hop's own
+FUSE_FIELDS = ("fused_frame", "fused_qw", "fused_qx", "fused_qy", "fused_qz", "fused_tx", "fused_ty", "fused_tz",
+               "fused_count", "rot_spread", "spread_u", "spread_v", "spread_z")
 
 
-def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, query_points=None, device="cuda"):
+def _stream_fuse(cfg, anchor):
+    """cfg.stream.fuse / fuse_weight -> (fuse, fuse_weight, anchor, CSV fields). Without an anchor the
+    fused poses are relative to the stream's first frame: identity rotation at the principal point,
+    depth 1, of cfg.stream.dataset (default "AMD") with cfg.stream.ratio (default 1.0)."""
+    fuse = bool(_get(cfg, "stream.fuse", False))
+    if not fuse:
+        return False, None, anchor, STREAM_FIELDS
+    if anchor is None:
+        from .models.utils import INTRINSICS
+        dataset = _get(cfg, "stream.dataset", "AMD")
+        fx, _, cx, cy = INTRINSICS[dataset]
+        anchor = ([1.0, 0.0, 0.0, 0.0], [cx, cy, 1.0], fx, float(_get(cfg, "stream.ratio", 1.0)), dataset)
+    return True, _get(cfg, "stream.fuse_weight", None), anchor, STREAM_FIELDS + FUSE_FIELDS
+
+
+def _fused_rows(r, positions):
+    """The FUSE_FIELDS columns of the window positions `positions` of a fused StreamResult."""
+    cols = torch.cat([r.fused_R.double(), r.fused_T, r.fused_count[:, None].double(), r.rot_spread[:, None].double(),
+                      r.trans_spread.double()], 1).tolist()
+    rows = []
+    for i in positions:
+        c = cols[i]
+        rows.append(dict(zip(FUSE_FIELDS, [r.frame_index + i] + c[:7] + [int(c[7])] + c[8:])))
+    return rows
+
+
+def _log_hop(logger, fields, r, window, ms, last=None):
+    """One hop's CSV rows. Without fusion: one row. With it: one row per final frame of the hop (the
+    hop's own columns repeated). last: the hop's row dict again, for the flush at the end of the
+    stream (the frames of the last window that no later hop made final)."""
+    if last is None:
+        enc = r.pred_pose_enc[-1].tolist()  # (synchronises: the events are complete after it)
+        row = dict(zip(STREAM_FIELDS, [r.frame_index, r.frame_index + window - 1] + enc + [ms]))
+        positions = range(r.final) if r.final is not None else None
+    else:
+        row, positions = last, range(r.final, window)
+    if positions is None:
+        logger.log(row)
+    else:
+        for extra in _fused_rows(r, positions):
+            logger.log({**row, **extra})
+    return row
+
+
+def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, query_points=None, device="cuda",
+                anchor=None):
     """Online evaluation of one long sequence (opt-in: cfg.stream.enable must be true; train_fn /
     test_fn never call it). frames_iter yields uint8 [H, W, 3] frames in order (sequence_stream);
     each is cropped to `box` and resized / normalised on the device (crop_resize_normalize, the
@@ -618,7 +666,11 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
     `query_points` [N, 2] for every window, else SuperPoint (+ SIFT) keypoints of each window's first
     frame. One CSV row per hop: the window's first frame, its newest frame, the newest frame's pose
     encoding relative to the first (du, dv, dd, quaternion) and the time of the push that completed
-    the hop (per-frame stages of the new frame + the hop), from device events. -> number of hops."""
+    the hop (per-frame stages of the new frame + the hop), from device events. -> number of hops.
+    anchor: the 5-tuple PoseStream takes. cfg.stream.fuse (default false; cfg.stream.fuse_weight: null
+    or "score") turns pose fusion on: the CSV gains the FUSE_FIELDS columns, one row per frame whose
+    fused pose is final (the first `stride` frames of each hop), and at the end of the stream one
+    flush writes the remaining frames of the last window. With fusion off the CSV is what it was."""
     from .data import crop_resize_normalize
     from .stream import PoseStream, keypoint_query
     if not _get(cfg, "stream.enable", False):
@@ -631,25 +683,29 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
         sp = sp if sp is not None else _keypoint_init(cfg, device)
         query_fn = keypoint_query(sp, sift=sift, track_num=_get(cfg, "train.track_num", 512))
     mp = _get(cfg, "mixed_precision", "no")
+    fuse, fuse_weight, anchor, fields = _stream_fuse(cfg, anchor)
     stream = PoseStream(model, window=window, stride=int(_get(cfg, "stream.stride", 1)),
-                        capacity=_get(cfg, "stream.capacity", None), query_fn=query_fn,
-                        precision=torch.bfloat16 if mp == "bf16" else torch.float32)
-    logger = CsvLogger(csv_path, STREAM_FIELDS)
+                        capacity=_get(cfg, "stream.capacity", None), query_fn=query_fn, anchor=anchor,
+                        precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight)
+    logger = CsvLogger(csv_path, fields)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    hops = 0
+    hops, last = 0, None
     for frame in frames_iter:
         up = torch.as_tensor(frame)[None].to(device)
         e0.record()
         results = stream.push(crop_resize_normalize(up, box, (size, size))[0], query_points=query_points)
         e1.record()
         for r in results:
-            enc = r.pred_pose_enc[-1].tolist()  # (synchronises: the events are complete after it)
-            logger.log(dict(zip(STREAM_FIELDS, [r.frame_index, r.frame_index + window - 1] + enc + [e0.elapsed_time(e1)])))
+            e1.synchronize()
+            last = (r, _log_hop(logger, fields, r, window, e0.elapsed_time(e1)))
             hops += 1
+    if fuse and last is not None:
+        _log_hop(logger, fields, last[0], window, None, last=last[1])
     return hops
 
 
-def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_points=None, device="cuda"):
+def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_points=None, device="cuda",
+                     anchors=None):
     """stream_eval for several sequences at a time (opt-in: cfg.stream.enable). `sequences` is an
     iterable of (name, frames_iter, box), each as stream_eval takes them; cfg.stream.streams
     (default 4) streams of one comet_amd.stream.StreamPool run side by side. Every free stream takes
@@ -657,7 +713,10 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
     sequence, and when a sequence ends the pool goes on with the streams that remain. One CSV per
     sequence, csv_dir/<name>.csv, with the rows stream_eval writes; hop_ms is the time of the push
     that completed the hop (the frames of all running streams and all hops due in it), from device
-    events. -> {name: number of hops}."""
+    events. -> {name: number of hops}. anchors: {sequence name: the 5-tuple PoseStream takes}.
+    cfg.stream.fuse / fuse_weight as stream_eval: the fused columns, and a flush of its last window
+    when a sequence ends (all hops of a push are fused by one launch; every anchor must then carry
+    one ratio and one dataset)."""
     from .data import crop_resize_normalize
     from .stream import StreamPool, keypoint_query
     if not _get(cfg, "stream.enable", False):
@@ -671,9 +730,16 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
         sp = sp if sp is not None else _keypoint_init(cfg, device)
         query_fn = keypoint_query(sp, sift=sift, track_num=_get(cfg, "train.track_num", 512))
     mp = _get(cfg, "mixed_precision", "no")
+    anchors = anchors or {}
+    fuse, fuse_weight, default_anchor, fields = _stream_fuse(cfg, None)
+    anchored = fuse or bool(anchors)
+    if anchored and default_anchor is None:
+        raise ValueError("stream_eval_pool: anchors without cfg.stream.fuse are not supported")
     pool = StreamPool(model, streams=S, window=window, stride=int(_get(cfg, "stream.stride", 1)),
                       capacity=_get(cfg, "stream.capacity", None), query_fn=query_fn,
-                      precision=torch.bfloat16 if mp == "bf16" else torch.float32)
+                      anchors=[default_anchor] * S if fuse else None,
+                      precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight)
+    lasts = {}  # stream id -> (last result, its row): flushed when the sequence ends
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     seqs = iter(sequences)
     running = {}  # stream id -> (name, frame iterator, box, logger)
@@ -687,12 +753,15 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
                 if nxt is None:
                     return None
                 name, frames_iter, box = nxt
-                pool.reset(sid)
-                running[sid] = (name, iter(frames_iter), box, CsvLogger(os.path.join(csv_dir, f"{name}.csv"), STREAM_FIELDS))
+                pool.reset(sid, anchor=anchors.get(name, default_anchor) if fuse else None)
+                running[sid] = (name, iter(frames_iter), box, CsvLogger(os.path.join(csv_dir, f"{name}.csv"), fields))
                 hops[name] = 0
             frame = next(running[sid][1], None)
             if frame is not None:
                 return frame
+            if fuse and sid in lasts:
+                r, row = lasts.pop(sid)
+                _log_hop(running[sid][3], fields, r, window, None, last=row)
             del running[sid]
 
     while True:
@@ -705,9 +774,9 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
         results = pool.push(frames, streams=[sid for sid, _ in new], query_points=query_points)
         e1.record()
         for sid, r in results:
-            enc = r.pred_pose_enc[-1].tolist()  # (synchronises: the events are complete after it)
+            e1.synchronize()
             name, logger = running[sid][0], running[sid][3]
-            logger.log(dict(zip(STREAM_FIELDS, [r.frame_index, r.frame_index + window - 1] + enc + [e0.elapsed_time(e1)])))
+            lasts[sid] = (r, _log_hop(logger, fields, r, window, e0.elapsed_time(e1)))
             hops[name] += 1
 
 

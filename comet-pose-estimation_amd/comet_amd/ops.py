@@ -4,6 +4,7 @@ Every function enqueues on torch's current HIP stream and returns device tensors
 has a CPU/PyTorch fallback: a missing library or an unsupported shape raises.
 """
 import ctypes
+from typing import NamedTuple
 
 import torch
 
@@ -640,6 +641,57 @@ def ring_scatter(pairs, slots, slots_host, max_blocks=0):
             "ring_scatter")
     if e0 is not None:
         PROF.stop(e0, "comet_ring_scatter", 0.0, float(2 * k * sum(r.slot_bytes for r in R)))
+
+
+class FuseOut(NamedTuple):
+    R: torch.Tensor             # [n, T, 4] f32 fused rotation (quaternion, w >= 0)
+    uvz: torch.Tensor           # [n, T, 3] f64 fused (u, v, z)
+    T: torch.Tensor             # [n, T, 3] f64 fused translation
+    count: torch.Tensor         # [n, T] int32 hypotheses fused so far
+    rot_spread: torch.Tensor    # [n, T] f32, radians
+    trans_spread: torch.Tensor  # [n, T, 3] f32, of (u, v, z)
+    hyp_R: torch.Tensor         # [n, T, 4] f32 this window's own hypothesis
+    hyp_T: torch.Tensor         # [n, T, 3] f64
+
+
+def pose_fuse(enc, acc, slots, slots_host, fresh, fresh_host, first, first_host, anchors, ratio, intr, weights=None):
+    """comet_pose_fuse (include/comet_hip.h): the n hops enc [n, T, 7] f32 update the accumulator
+    ring acc [rows, 20] f64 in place -> FuseOut, all in one launch. slots / fresh / first: int32
+    device tensors of n * T / n / n entries, *_host the same values as ctypes int32 arrays (checked by
+    the library before it launches); anchors [n, 7] f64 (q[4], u, v, z), read for first hops only;
+    weights [n, T] f32 or None (= 1); ratio as pose_decode takes it; intr = (fx, fy, cx, cy)."""
+    _req_cuda(enc, acc, slots, fresh, first, anchors, weights)
+    if enc.dim() != 3 or enc.shape[2] != 7 or enc.dtype != torch.float32 or not enc.is_contiguous():
+        raise L.CometHipError(f"pose_fuse: enc must be a dense f32 [n, T, 7] tensor, got {tuple(enc.shape)} {enc.dtype}")
+    n, T = enc.shape[:2]
+    if acc.dim() != 2 or acc.shape[1] != L.FUSE_ROW or acc.dtype != torch.float64 or not acc.is_contiguous():
+        raise L.CometHipError(f"pose_fuse: acc must be a dense f64 [rows, {L.FUSE_ROW}] tensor")
+    for name, t, host, count in (("slots", slots, slots_host, n * T), ("fresh", fresh, fresh_host, n),
+                                 ("first", first, first_host, n)):
+        if t.dtype != torch.int32 or t.numel() != count or not t.is_contiguous() or len(host) != count:
+            raise L.CometHipError(f"pose_fuse: {name} must be a dense int32 device tensor of {count} entries with a "
+                                  "host copy of the same length")
+    if anchors.shape != (n, 7) or anchors.dtype != torch.float64 or not anchors.is_contiguous():
+        raise L.CometHipError("pose_fuse: anchors must be a dense f64 [n, 7] tensor")
+    if weights is not None and (weights.shape != (n, T) or weights.dtype != torch.float32 or not weights.is_contiguous()):
+        raise L.CometHipError("pose_fuse: weights must be a dense f32 [n, T] tensor")
+    if any(t.device != enc.device for t in (acc, slots, fresh, first, anchors) + (() if weights is None else (weights,))):
+        raise L.CometHipError("pose_fuse: every tensor must be on one device")
+    dev = enc.device
+    out = FuseOut(torch.empty(n, T, 4, device=dev), torch.empty(n, T, 3, device=dev, dtype=torch.float64),
+                  torch.empty(n, T, 3, device=dev, dtype=torch.float64), torch.empty(n, T, device=dev, dtype=torch.int32),
+                  torch.empty(n, T, device=dev), torch.empty(n, T, 3, device=dev), torch.empty(n, T, 4, device=dev),
+                  torch.empty(n, T, 3, device=dev, dtype=torch.float64))
+    fx, fy, cx, cy = intr
+    rh, keep, rd = _ratio_args(ratio)
+    e0 = PROF.start()
+    L.check(L.load().comet_pose_fuse(_p(enc), _p(slots), ctypes.addressof(slots_host), _p(fresh),
+                                     ctypes.addressof(fresh_host), _p(first), ctypes.addressof(first_host),
+                                     _p(anchors), _p(weights), rh, rd, fx, fy, cx, cy, _p(acc), acc.shape[0], n, T,
+                                     *[_p(t) for t in out], stream()), "pose_fuse")
+    if e0 is not None:
+        PROF.stop(e0, "comet_pose_fuse", 0.0, float(n * T * (2 * 8 * L.FUSE_ROW + 28 + 120)))
+    return out
 
 
 def resize_bilinear_pool(x, oh, ow):

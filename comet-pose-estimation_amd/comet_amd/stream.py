@@ -13,6 +13,9 @@ them once per frame, keeps their outputs in device rings, and for every hop gath
   PoolSchedule   the same arithmetic for S streams over pooled rings, host only
   StreamPool     S streams on one model: push(one frame per stream) runs the per-frame stages, the
                  ring store (comet_ring_scatter) and the hops that fall due as one batch each
+  FuseSchedule   which hop is a stream's first, which window positions are new / final, host only
+  PoseFuser      one fused pose per frame from the overlapping windows (comet_pose_fuse, one launch
+                 per push); usable on its own with any [n, T, 7] encodings
   keypoint_query query_fn from the SuperPoint / SIFT detectors of comet_amd.keypoints
 """
 import ctypes
@@ -81,6 +84,13 @@ class StreamResult(NamedTuple):
     pred_score: Optional[torch.Tensor]   # [T, N]
     R: Optional[torch.Tensor] = None   # [T, 4] absolute quaternions (anchor given)
     T: Optional[torch.Tensor] = None   # [T, 3] absolute translations, float64 (anchor given)
+    # fuse=True only: one pose per frame from every window that has seen it so far (PoseFuser)
+    fused_R: Optional[torch.Tensor] = None       # [T, 4]
+    fused_T: Optional[torch.Tensor] = None       # [T, 3] float64
+    fused_count: Optional[torch.Tensor] = None   # [T] int32, hypotheses fused
+    rot_spread: Optional[torch.Tensor] = None    # [T] radians
+    trans_spread: Optional[torch.Tensor] = None  # [T, 3], of (u, v, z)
+    final: Optional[int] = None  # the leading positions whose fused pose will not change again
 
 
 class Anchor(NamedTuple):
@@ -127,6 +137,154 @@ def _decode_chained(a, ref, ratio, s, enc, T):
     return R, Tx, ref
 
 
+class FuseSchedule:
+    """The host-only arithmetic of pose fusion for `streams` streams of one window / stride. A
+    stream's first hop (after construction or reset) is decoded against its anchor and every
+    position of it is new: fresh_from = 1. In a later hop the positions [window - stride, window)
+    are frames no earlier window has seen (fresh_from = window - stride; their accumulator rows are
+    overwritten, the others added to). The first `final` = stride positions of any hop appear in no
+    later window: their fused pose will not change again."""
+
+    def __init__(self, window, stride=1, streams=1):
+        if stride < 1 or stride >= window:
+            raise ValueError(f"pose fusion needs 1 <= stride < window (stride {stride}, window {window}): the next "
+                             "window's first frame must lie inside the current window")
+        if streams < 1:
+            raise ValueError(f"at least 1 stream, got {streams}")
+        self.window, self.stride, self.streams = int(window), int(stride), int(streams)
+        self._first = [True] * self.streams
+
+    @property
+    def final(self):
+        return self.stride
+
+    def reset(self, stream=None):
+        for s in (range(self.streams) if stream is None else [self._id(stream)]):
+            self._first[s] = True
+
+    def _id(self, stream):
+        s = int(stream)
+        if not 0 <= s < self.streams:
+            raise ValueError(f"unknown stream {s}: the schedule has streams 0 .. {self.streams - 1}")
+        return s
+
+    def is_first(self, stream=0):
+        """Whether the next hop of the stream is its first (nothing is advanced)."""
+        return self._first[self._id(stream)]
+
+    def hop(self, stream=0):
+        """Account for one hop of the stream -> (first, fresh_from)."""
+        s = self._id(stream)
+        first = self._first[s]
+        self._first[s] = False
+        return first, (1 if first else self.window - self.stride)
+
+
+class PoseFuser:
+    """One pose per frame from overlapping windows (DESIGN.md "Pose fusion").
+
+        fuser = PoseFuser(window=T, stride=1, anchors=[(R0 [4], T_uvz0 [3])], ratio=ratio, intr=(fx, fy, cx, cy))
+        out = fuser.fuse(enc, [(0, hop)])        # enc [1, T, 7]; hop: the Hop RingSchedule.push gave
+
+    Owns the accumulator ring acc [streams * capacity, 20] float64 on the device (row of frame f of
+    stream s: s * capacity + f % capacity, the slot numbering of the frame rings) and a FuseSchedule.
+    fuse() is one comet_pose_fuse launch for all the hops given (at most one per stream): each hop is
+    referenced to the fused pose of its first frame (its anchor for a stream's first hop), every
+    frame's row takes the hop's hypothesis, and the fused pose, count and spread of every frame of
+    every hop come back (ops.FuseOut, [n, T, ...]). The small per-hop int32 tables are cached on the
+    device by their values, so a steady-state call uploads nothing. Fusion reduces the drift of
+    single-estimate chaining, it does not remove it: there is no loop closure and no global
+    optimisation, and as stride approaches window / 2 the chained frame has one hypothesis only and
+    nothing is gained."""
+
+    _TABLES_MAX = 1024
+
+    def __init__(self, window, stride=1, capacity=None, streams=1, anchors=None, ratio=1.0, intr=None, device="cuda"):
+        self.ring = PoolSchedule(streams, window, stride, capacity)
+        self.sched = FuseSchedule(window, stride, streams)
+        if intr is None or len(intr) != 4:
+            raise ValueError("PoseFuser needs intr = (fx, fy, cx, cy)")
+        self.ratio, self.intr = ratio, tuple(float(v) for v in intr)
+        self.device = torch.device(device)
+        self.acc = torch.zeros(self.ring.streams * self.ring.capacity, 20, dtype=torch.float64, device=self.device)
+        self._anchors = torch.zeros(self.ring.streams, 7, dtype=torch.float64)  # host; rows go up by stream tuple
+        self._anchors[:, 0] = 1.0
+        self._set = [False] * self.ring.streams
+        self._tables, self._anchor_rows = {}, {}
+        if anchors is not None:
+            for s, a in (anchors.items() if isinstance(anchors, dict) else enumerate(anchors)):
+                self.set_anchor(s, a[0], a[1])
+
+    def set_anchor(self, stream, R, T_uvz):
+        """The pose of the stream's first frame: R [4] quaternion, T_uvz [3]; read by its next first hop."""
+        s = self.sched._id(stream)
+        row = torch.cat([torch.as_tensor(R).detach().double().reshape(4).cpu(),
+                         torch.as_tensor(T_uvz).detach().double().reshape(3).cpu()])
+        self._anchors[s] = row
+        self._set[s] = True
+        self._anchor_rows.clear()
+
+    def reset(self, stream=None):
+        """The next hop of `stream` (default: of every stream) is a first hop again, at its anchor.
+        Its rows need no clearing: a first hop overwrites every row it touches."""
+        self.sched.reset(stream)
+
+    def _table(self, values):
+        key = tuple(values)
+        hit = self._tables.get(key)
+        if hit is None:
+            if len(self._tables) >= self._TABLES_MAX:
+                self._tables.clear()
+            hit = (torch.tensor(key, dtype=torch.int32, device=self.device), (ctypes.c_int32 * len(key))(*key))
+            self._tables[key] = hit
+        return hit
+
+    def fuse(self, enc, hops, weights=None):
+        """enc [n, T, 7] f32 (or [n * T, 7]) of the n hops `hops` = [(stream, Hop)], weights [n, T]
+        f32 or None -> ops.FuseOut. The streams must be distinct."""
+        T = self.ring.window
+        ids = tuple(self.sched._id(s) for s, _ in hops)
+        n = len(ids)
+        if n == 0 or len(set(ids)) != n:
+            raise ValueError(f"fuse takes at least one hop and one hop per stream, got the streams {list(ids)}")
+        if enc.numel() != n * T * 7:
+            raise ValueError(f"{n} hops of window {T} need enc [{n}, {T}, 7], got {tuple(enc.shape)}")
+        missing = [s for s in ids if self.sched.is_first(s) and not self._set[s]]
+        if missing:
+            raise ValueError(f"no anchor for the streams {missing}, whose first hop this is")
+        flags = [(self.sched.is_first(s), 1 if self.sched.is_first(s) else T - self.sched.stride) for s in ids]
+        slots, slots_host = self._table(self.ring.table(list(hops)))
+        fresh, fresh_host = self._table([f for _, f in flags])
+        first, first_host = self._table([int(f) for f, _ in flags])
+        rows = self._anchor_rows.get(ids)
+        if rows is None:
+            rows = self._anchor_rows[ids] = self._anchors[list(ids)].contiguous().to(self.device)
+        out = ops.pose_fuse(enc.view(n, T, 7), self.acc, slots, slots_host, fresh, fresh_host, first, first_host, rows,
+                            self.ratio, self.intr, weights)
+        for s in ids:  # (only a launch that went out advances the schedule)
+            self.sched.hop(s)
+        return out
+
+
+def _score_weights(sc):
+    """fuse_weight="score": pred_score [n, T, N] -> weights [n, T], the mean over the tracks, at least 1e-6."""
+    if sc is None:
+        raise RuntimeError('fuse_weight="score" needs the model\'s pred_score output')
+    return sc.float().mean(-1).clamp_min(1e-6).contiguous()
+
+
+def _check_fuse(fuse, fuse_weight, anchored):
+    if fuse_weight not in (None, "score"):
+        raise ValueError(f'fuse_weight must be None or "score", got {fuse_weight!r}')
+    if fuse and not anchored:
+        raise ValueError("fuse=True needs an anchor: fused poses are absolute")
+
+
+def _fused_fields(out, b, final):
+    return dict(R=out.hyp_R[b], T=out.hyp_T[b], fused_R=out.R[b], fused_T=out.T[b], fused_count=out.count[b],
+                rot_spread=out.rot_spread[b], trans_spread=out.trans_spread[b], final=final)
+
+
 class PoseStream:
     """Sliding-window pose estimation over a frame stream.
 
@@ -149,15 +307,32 @@ class PoseStream:
     stride < window is required). That frame's (u, v, z) is rounded to the codec's f32 before it
     becomes the reference, and the earlier window's result reports the rounded pose, so a frame that
     is a window's first frame has one pose in both results. Errors of successive references add up:
-    the drift accumulates over the stream and is not corrected.
+    every hop adds a full single-window error to the reference, and without fusion nothing reduces it.
+
+    fuse=True (needs an anchor, so stride < window) makes use of the overlap: with stride < window a
+    frame lies in up to ceil(window / stride) windows, and one comet_pose_fuse launch per hop
+    (PoseFuser) keeps a running weighted mean of all its hypotheses. Each window is then referenced
+    to the fused pose of its first frame, not to one earlier estimate, and every result carries
+    fused_R / fused_T (one pose per frame so far), fused_count, rot_spread (radians) and trans_spread
+    (of u, v, z); the first `final` = stride positions will not change again. R / T are still this
+    window's own hypothesis, against the fused reference. fuse_weight="score" weights position i by
+    the mean of pred_score[i] over the tracks (at least 1e-6); None weights every hypothesis 1. Fusion
+    reduces the drift (DESIGN.md "Pose fusion": to about 0.2 - 0.35 of chaining at stride <= window / 4)
+    and does not remove it: there is no loop closure and no global optimisation, and the gain
+    vanishes as stride approaches window / 2, where the chained frame has a single hypothesis.
+    _decode_chained is not called when fuse is on; with fuse=False nothing changes.
 
     One stream (batch 1). The model is used as is (its eval / train mode included)."""
 
-    def __init__(self, model, window, stride=1, capacity=None, query_fn=None, anchor=None, precision=None):
+    def __init__(self, model, window, stride=1, capacity=None, query_fn=None, anchor=None, precision=None,
+                 fuse=False, fuse_weight=None):
         self.model = model
         self.sched = RingSchedule(window, stride, capacity)
         self.query_fn = query_fn
         self.precision = precision if precision is not None else _model_precision(model)
+        _check_fuse(fuse, fuse_weight, anchor is not None)
+        self.fuse, self.fuse_weight = bool(fuse), fuse_weight
+        self._fuser = None
         self.anchor = None
         if anchor is not None:
             self.sched.chain_index()  # raises unless stride < window
@@ -171,6 +346,8 @@ class PoseStream:
         self._wins = None    # the gathered window, same order, [window, ...]
         self._hw = None
         self._ref = None     # (R [4] f32, T_uvz [3] f32) the next hop is decoded against
+        if self._fuser is not None:
+            self._fuser.reset()
 
     # -- ring -------------------------------------------------------------------------------------
     @staticmethod
@@ -228,9 +405,13 @@ class PoseStream:
         tr = out.get("pred_tracks")
         sc = out.get("_track_predictions", {}).get("pred_score")
         R = Tx = None
+        res = StreamResult(hop.frame_index, enc, None if tr is None else tr[0], None if sc is None else sc[0])
+        if self.fuse:
+            w = _score_weights(sc) if self.fuse_weight == "score" else None
+            return res._replace(**_fused_fields(self._fuser.fuse(enc, [(0, hop)], w), 0, self._fuser.sched.final))
         if self.anchor is not None:
             R, Tx = self._decode(enc, T)
-        return StreamResult(hop.frame_index, enc, None if tr is None else tr[0], None if sc is None else sc[0], R, Tx)
+        return res._replace(R=R, T=Tx)
 
     @torch.no_grad()
     def push(self, frames, query_points=None):
@@ -251,7 +432,13 @@ class PoseStream:
             if self._rings is None:
                 self._allocate(per, frames.device)
                 self._hw = hw
-                if self.anchor is not None:
+                if self.fuse:
+                    if self._fuser is None or self._fuser.device != frames.device:
+                        from .models.utils import INTRINSICS
+                        a = self.anchor
+                        self._fuser = PoseFuser(self.sched.window, self.sched.stride, self.sched.capacity, 1,
+                                                [(a.R, a.T_uvz)], a.ratio, INTRINSICS[a.dataset], frames.device)
+                elif self.anchor is not None:
                     self._ref, self._ratio = _anchor_ref(self.anchor, frames.device)
             for i in range(frames.shape[0]):
                 slot, hop = self.sched.push()
@@ -361,18 +548,25 @@ class StreamPool:
     (filter_and_pad returns between min_required and track_num points) are grouped by N, one
     batched call per group. anchors: a dict or list giving every stream the 5-tuple PoseStream
     takes; each stream chains its absolute poses as PoseStream does (decoded per stream by the same
-    code, so for the same pred_pose_enc the same bits).
+    code, so for the same pred_pose_enc the same bits). fuse / fuse_weight: as PoseStream's; all the
+    hops due in a push, of every query-count group, are fused by one comet_pose_fuse launch. With
+    fuse=True every anchor must carry the same ratio and dataset (one launch takes one ratio and one
+    set of intrinsics).
 
     push() -> [(stream id, StreamResult)] ordered by stream id. The tensors of a result are views
     of the batched outputs. The model is used as is (its eval / train mode included)."""
 
     _TABLES_MAX = 1024  # cached device slot tables (periodic in capacity for streams in phase)
 
-    def __init__(self, model, streams, window, stride=1, capacity=None, query_fn=None, anchors=None, precision=None):
+    def __init__(self, model, streams, window, stride=1, capacity=None, query_fn=None, anchors=None, precision=None,
+                 fuse=False, fuse_weight=None):
         self.model = model
         self.sched = PoolSchedule(streams, window, stride, capacity)
         self.query_fn = query_fn
         self.precision = precision if precision is not None else _model_precision(model)
+        _check_fuse(fuse, fuse_weight, anchors is not None)
+        self.fuse, self.fuse_weight = bool(fuse), fuse_weight
+        self._fuser = None
         self.anchors = None
         if anchors is not None:
             self.sched.scheds[0].chain_index()  # raises unless stride < window
@@ -382,13 +576,37 @@ class StreamPool:
                 raise ValueError(f"anchors must name every stream 0 .. {self.sched.streams - 1}, got "
                                  f"{sorted(self.anchors)}")
         self._ratios = {}
+        if self.fuse:
+            self._fuse_key = self._anchor_key(self.anchors[0])
+            for a in self.anchors.values():
+                self._same_key(a)
         self.reset()
 
-    def reset(self, stream=None):
-        """reset(s): stream s forgets its frames (its next frame is frame 0, at its anchor); the
-        other streams go on. reset(): every stream, and the rings are dropped (a new frame size may
-        follow)."""
+    @staticmethod
+    def _anchor_key(a):
+        return float(torch.as_tensor(a.ratio, dtype=torch.float64).reshape(-1)[0]), a.dataset
+
+    def _same_key(self, a):
+        if self._anchor_key(a) != self._fuse_key:
+            raise ValueError(f"fuse=True needs one ratio and one dataset for all anchors, got {self._anchor_key(a)} "
+                             f"and {self._fuse_key}")
+
+    def reset(self, stream=None, anchor=None):
+        """reset(s): stream s forgets its frames (its next frame is frame 0, at its anchor, or at
+        `anchor` when one is given); the other streams go on. reset(): every stream, and the rings are
+        dropped (a new frame size may follow)."""
         self.sched.reset(stream)
+        if anchor is not None:
+            if stream is None or self.anchors is None:
+                raise ValueError("reset(stream, anchor=...) replaces the anchor of one stream of an anchored pool")
+            a = Anchor(*anchor)
+            if self.fuse:
+                self._same_key(a)
+                if self._fuser is not None:
+                    self._fuser.set_anchor(stream, a.R, a.T_uvz)
+            self.anchors[int(stream)] = a
+        if self._fuser is not None:
+            self._fuser.reset(stream)
         if stream is None:
             self._rings = self._wins = self._hw = self._dev = None
             self._tables = {}
@@ -412,6 +630,11 @@ class StreamPool:
             self._rings.append(torch.empty(S * cap, *slot, device=dev, dtype=t.dtype))
             self._wins.append(torch.empty(S * T, *slot, device=dev, dtype=t.dtype))
         self._dev = dev
+        if self.fuse and (self._fuser is None or self._fuser.device != dev):
+            from .models.utils import INTRINSICS
+            ratio, dataset = self._fuse_key
+            self._fuser = PoseFuser(T, self.sched.stride, cap, S, {s: (a.R, a.T_uvz) for s, a in self.anchors.items()},
+                                    ratio, INTRINSICS[dataset], dev)
 
     def _table(self, values):
         """A slot table on the device (int32) and on the host (ctypes), cached by its values."""
@@ -439,9 +662,10 @@ class StreamPool:
         return R, Tx
 
     # -- hops -------------------------------------------------------------------------------------
-    def _hops(self, hops, qs, pos):
+    def _hops(self, hops, qs, pos, fused=None):
         """The hops hops[i], i in pos (all with N query points) as one batched call ->
-        [(stream, StreamResult)] in the order of pos."""
+        [(stream, StreamResult)] in the order of pos. fused (fuse=True): a list that takes the
+        group's (pred_pose_enc, pred_score); the absolute poses are then left to _fuse."""
         from .models.E2Epose2 import FrameCache
         T, n = self.sched.window, len(pos)
         table, table_host = self._table(self.sched.table([hops[i] for i in pos]))
@@ -457,15 +681,29 @@ class StreamPool:
         tr = out.get("pred_tracks")
         sc = out.get("_track_predictions", {}).get("pred_score")
         results = []
+        if fused is not None:
+            fused.append((enc, sc))
         for b, i in enumerate(pos):
             sid, hop = hops[i]
             e = enc[b * T:(b + 1) * T]
             R = Tx = None
-            if self.anchors is not None:
+            if self.anchors is not None and fused is None:
                 R, Tx = self._decode(sid, e, T)
             results.append((sid, StreamResult(hop.frame_index, e, None if tr is None else tr[b],
                                               None if sc is None else sc[b], R, Tx)))
         return results
+
+    def _fuse(self, hops, results, fused):
+        """One comet_pose_fuse launch for all the hops of a push: hops in the order of `results`,
+        fused = [(pred_pose_enc, pred_score)] per query-count group."""
+        enc = fused[0][0] if len(fused) == 1 else torch.cat([e for e, _ in fused])
+        w = None
+        if self.fuse_weight == "score":
+            ws = [_score_weights(sc) for _, sc in fused]
+            w = ws[0] if len(ws) == 1 else torch.cat(ws)
+        out = self._fuser.fuse(enc, hops, w)
+        final = self._fuser.sched.final
+        return [(sid, r._replace(**_fused_fields(out, b, final))) for b, (sid, r) in enumerate(results)]
 
     @torch.no_grad()
     def push(self, frames, streams=None, query_points=None):
@@ -498,8 +736,12 @@ class StreamPool:
                              slot_table, slot_host)
             if hops:
                 qs = [self._query(sid, hop, query_points) for sid, hop in hops]
+                fused, order = ([] if self.fuse else None), []
                 for _, pos in self.sched.group([q.shape[0] for q in qs]):
-                    results += self._hops(hops, qs, pos)
+                    results += self._hops(hops, qs, pos, fused)
+                    order += pos
+                if self.fuse:
+                    results = self._fuse([hops[i] for i in order], results, fused)
         return sorted(results, key=lambda r: r[0])
 
 

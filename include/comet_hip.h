@@ -533,6 +533,41 @@ int comet_ring_gather(const CometRingTensor* tensors, int n_tensors, const int32
 int comet_ring_scatter(const CometRingTensor* tensors, int n_tensors, const int32_t* slots,
                        const int32_t* slots_host, int k, int capacity, int max_blocks, void* stream);
 
+/* comet_pose_fuse (DESIGN.md "Pose fusion"): with stride < window a frame lies in several windows;
+ *   this keeps one accumulator row per ring slot and returns, for every frame of the n hops of a
+ *   push, ONE fused pose with a count and a spread, in one launch. acc [rows, COMET_FUSE_ROW] f64,
+ *   row of frame f of stream s = s * capacity + f % capacity (the slot numbering of the frame
+ *   rings, so `slots` / `slots_host` are the gather's tables, n * T entries). Row layout:
+ *     0 W = sum w | 1..10 upper triangle of sum w q q^T (ww wx wy wz xx xy xz yy yz zz, q unit, in
+ *     double) | 11..13 sum w (u, v, z) | 14..16 sum w (u^2, v^2, z^2) | 17 count | 18, 19 zero.
+ *   enc [n * T, 7] f32, relative to each window's first frame. Per hop h: first[h] = 1 for a
+ *   stream's first hop (the reference is anchors[h] = (q[4], u, v, z) f64, which also becomes row
+ *   slots[h * T] as one hypothesis of weight 1), else 0 (the reference is the fused pose of row
+ *   slots[h * T]; anchors[h] is not read); fresh_from[h] = 1 for a first hop, T - stride afterwards.
+ *   One thread per (h, i): hypothesis q = normalise(enc[3:7] (x) q_ref), w >= 0; u = u_ref +
+ *   e0 / ratio * 128, v likewise, z = z_ref * (e2 / ratio + 1), all double (the codec's composition,
+ *   comet_pose_decode). For i >= 1 the row is overwritten by the hypothesis when i >= fresh_from[h],
+ *   else the hypothesis is added; position 0 is written by a first hop only. weights [n * T] f32 > 0
+ *   or NULL (= 1). ratio / ratio_dev as comet_pose_decode. Outputs per (h, i), from the row after
+ *   the update: R [4] f32 = eigenvector of the largest eigenvalue of the 4 x 4 matrix (fixed-sweep
+ *   cyclic Jacobi in double; lowest index among equal eigenvalues; w >= 0), uvz [3] f64 = sum w x / W,
+ *   T [3] f64 = ((u - cx) z / fx, (v - cy) z / fy, z), count int32, rot_spread f32 =
+ *   2 asin(sqrt(max(0, 1 - lambda_max / W))) rad, trans_spread [3] f32 = sqrt(max(0, E[x^2] - E[x]^2));
+ *   and the window's own hypothesis hyp_R [4] f32, hyp_T [3] f64 (as T, from the hypothesis).
+ *   COMET_EINVAL before anything is launched: a null pointer (weights and ratio_dev may be null),
+ *   n <= 0, T < 2, rows <= 0, fresh_from outside [1, T], first not 0 / 1 or 1 with fresh_from != 1,
+ *   a host slot outside [0, rows), two equal host slots (two positions for one row would race; a
+ *   stream completes at most one hop per push), a host ratio that is not finite and positive. The
+ *   kernel skips a slot outside [0, rows) and writes only inside acc and the outputs. */
+#define COMET_FUSE_ROW 20
+int comet_pose_fuse(const float* enc, const int32_t* slots, const int32_t* slots_host,
+                    const int32_t* fresh_from, const int32_t* fresh_from_host, const int32_t* first,
+                    const int32_t* first_host, const double* anchors, const float* weights, double ratio,
+                    const double* ratio_dev, double fx, double fy, double cx, double cy, double* acc,
+                    int rows, int n, int T, float* R_out, double* uvz_out, double* T_out,
+                    int32_t* count_out, float* rot_spread, float* trans_spread, float* hyp_R,
+                    double* hyp_T, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Debug support (bounds asserts and a NaN / Inf check mode).
  * comet_count_nonfinite: adds the number of NaN / Inf elements of x (n elements, dtype) to

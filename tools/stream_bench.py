@@ -21,6 +21,13 @@ S. Every stream has its own frames; all are in phase, so every timed push comple
                 a caller without the pool runs);
   (c) scatter   the comet_ring_scatter launch of a push alone, into a scratch ring (with the bytes it
                 moves: achieved bandwidth).
+(a) and (b) alternate push by push in one process; device events, medians and minima.
+
+--fuse: pose fusion (comet_pose_fuse, DESIGN.md "Pose fusion") against the chained decode it replaces.
+Two anchored streams (with --streams: two anchored pools of S streams) take the same frames,
+  (a) fuse on   one comet_pose_fuse launch per push for the absolute poses;
+  (b) fuse off  two comet_pose_decode launches and the torch arithmetic of _decode_chained per hop;
+  (c) kernel    the comet_pose_fuse launch of a push alone, on a scratch PoseFuser.
 (a) and (b) alternate push by push in one process; device events, medians and minima."""
 import argparse
 import json
@@ -94,6 +101,58 @@ def pool_bench(model, n_streams, args, dev):
         "data": "synthetic (N(0,1) frames, U[0,S-1] query points); random-init weights"}), flush=True)
 
 
+def fuse_bench(model, n_streams, args, dev):
+    """--fuse: n_streams = 0 times PoseStream, else StreamPool with that many streams."""
+    from comet_amd.models.utils import INTRINSICS
+    from comet_amd.stream import Hop, PoseFuser, PoseStream, StreamPool
+    T, S, N = args.frames, args.image, args.tracks
+    k = max(n_streams, 1)
+    g = torch.Generator(device=dev).manual_seed(1)
+    total = T + args.warmup + args.hops - 1
+    frames = torch.randn(total, k, 3, S, S, device=dev, generator=g)
+    q = torch.rand(N, 2, device=dev, generator=g) * (S - 1)
+    R0 = torch.tensor([0.8, 0.2, -0.4, 0.4], device=dev)
+    anchor = (R0 / R0.norm(), torch.tensor([331.25, 247.5, 11.375], device=dev), 268.44, 0.5, "AMD")
+    if n_streams == 0:
+        objs = {f: PoseStream(model, window=T, stride=1, anchor=anchor, precision=torch.bfloat16, fuse=f)
+                for f in (True, False)}
+        push = lambda f, i: objs[f].push(frames[i, 0], query_points=q)
+    else:
+        objs = {f: StreamPool(model, streams=k, window=T, stride=1, anchors=[anchor] * k, precision=torch.bfloat16, fuse=f)
+                for f in (True, False)}
+        push = lambda f, i: [r for _, r in objs[f].push(frames[i], query_points=q)]
+    for i in range(T - 1):
+        assert push(True, i) == [] and push(False, i) == []
+    scratch = PoseFuser(T, 1, T, k, [(anchor[0], anchor[1])] * k, 0.5, INTRINSICS["AMD"], dev)
+    ta, tb, tc, err = [], [], [], 0.0
+    for j in range(args.warmup + args.hops):
+        i = j + T - 1
+        order = (True, False) if j % 2 == 0 else (False, True)  # (neither path always runs first)
+        ms, res = {}, {}
+        for f in order:
+            ms[f], res[f] = _timed(lambda: push(f, i))
+        assert len(res[True]) == len(res[False]) == k
+        enc = torch.stack([r.pred_pose_enc for r in res[True]])
+        hops = [(s, Hop(j, j % T)) for s in range(k)]
+        ms_c, _ = _timed(lambda: [scratch.fuse(enc, hops) for _ in range(GATHER_REPS)])
+        if j >= args.warmup:
+            ta.append(ms[True])
+            tb.append(ms[False])
+            tc.append(ms_c / GATHER_REPS)
+            for a, b in zip(res[True], res[False]):
+                err = max(err, float((a.pred_pose_enc - b.pred_pose_enc).abs().max()))
+    a, b, c = statistics.median(ta), statistics.median(tb), statistics.median(tc)
+    print(json.dumps({
+        "metric": f"ms per push, pose fusion on against off, {'PoseStream' if n_streams == 0 else f'StreamPool of {k} streams'}, "
+                  f"T={T} {S}^2 N={N}, bf16, stride 1",
+        "streams": n_streams, "fuse_on_ms": round(a, 3), "fuse_off_ms": round(b, 3), "on_over_off": round(a / b, 4),
+        "min_fuse_on_ms": round(min(ta), 3), "min_fuse_off_ms": round(min(tb), 3),
+        "pose_fuse_ms": round(c, 4), "min_pose_fuse_ms": round(min(tc), 4), "pose_fuse_hops_per_launch": k,
+        "pose_fuse_timing": f"device events around {GATHER_REPS} back-to-back launches / {GATHER_REPS}, median over the pushes",
+        "pushes": args.hops, "warmup": args.warmup, "max_abs_pose_enc_diff_on_vs_off": err,
+        "data": "synthetic (N(0,1) frames, U[0,S-1] query points); random-init weights"}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16, help="window length T")
@@ -103,6 +162,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--streams", type=str, default=None,
                     help="comma-separated stream counts: time StreamPool against that many separate PoseStream objects")
+    ap.add_argument("--fuse", action="store_true",
+                    help="time pose fusion on against off (PoseStream, or StreamPool with --streams)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         print("stream_bench: no GPU", file=sys.stderr)
@@ -115,6 +176,10 @@ def main():
     cfg = load_config()
     torch.manual_seed(0)
     model = instantiate(cfg.MODEL, _recursive_=False, cfg=cfg).to(dev).eval()
+    if args.fuse:
+        for n_streams in ([0] if args.streams is None else [int(v) for v in args.streams.split(",")]):
+            fuse_bench(model, n_streams, args, dev)
+        return 0
     if args.streams is not None:
         for n_streams in [int(v) for v in args.streams.split(",")]:
             pool_bench(model, n_streams, args, dev)
