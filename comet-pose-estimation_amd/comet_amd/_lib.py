@@ -93,6 +93,7 @@ class RingTensor(ctypes.Structure):
 
 RING_MAX_TENSORS = 4  # COMET_RING_MAX_TENSORS
 FUSE_ROW = 20         # COMET_FUSE_ROW: doubles per accumulator row of comet_pose_fuse
+CARRY_MAX_TRACKS, CARRY_MAX_CANDIDATES, CARRY_MAX_CELLS = 4096, 65536, 8192  # COMET_CARRY_MAX_*
 
 # (name, restype, argtypes); every exported symbol of include/comet_hip.h
 _F = ctypes.c_float
@@ -187,6 +188,8 @@ SIGNATURES = {
     "comet_pose_fuse": (_INT, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_double, c_vp,
                                ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp,
                                _INT, _INT, _INT, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "comet_track_carry": (_INT, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _INT, _INT, _INT, _INT, _INT,
+                                 _INT, _INT, _INT, _INT, _F, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

@@ -627,6 +627,33 @@ def _stream_fuse(cfg, anchor):
     return True, _get(cfg, "stream.fuse_weight", None), anchor, STREAM_FIELDS + FUSE_FIELDS
 
 
+# cfg.stream.carry: these columns after all others, per hop
+CARRY_FIELDS = ("survivors", "born", "padded")
+
+
+def _stream_carry(cfg, sp, sift, candidate_fn, device):
+    """cfg.stream.carry (default false) / carry_tracks (default cfg.train.track_num) / carry_cell (8) /
+    carry_border (0) / carry_min_score (required) / detect_every (1) -> the carry keywords of PoseStream
+    / StreamPool ({} with carry off). candidate_fn: default keypoint_candidates of the detectors."""
+    if not _get(cfg, "stream.carry", False):
+        return {}
+    from .stream import keypoint_candidates
+    if candidate_fn is None:
+        candidate_fn = keypoint_candidates(sp if sp is not None else _keypoint_init(cfg, device), sift)
+    return dict(carry=True, carry_tracks=int(_get(cfg, "stream.carry_tracks", _get(cfg, "train.track_num", 512))),
+                carry_cell=int(_get(cfg, "stream.carry_cell", 8)), carry_border=int(_get(cfg, "stream.carry_border", 0)),
+                carry_min_score=_get(cfg, "stream.carry_min_score", None),
+                detect_every=int(_get(cfg, "stream.detect_every", 1)), candidate_fn=candidate_fn)
+
+
+def _carry_counts(r):
+    """(survivors, born, padded) of a carried StreamResult, from track_src (ops.CarryOut)."""
+    src = r.track_src.tolist()
+    survivors = sum(1 for j, v in enumerate(src) if v == j)
+    born = sum(1 for v in src if -1 - 65536 < v < 0)
+    return survivors, born, len(src) - survivors - born
+
+
 def _fused_rows(r, positions):
     """The FUSE_FIELDS columns of the window positions `positions` of a fused StreamResult."""
     cols = torch.cat([r.fused_R.double(), r.fused_T, r.fused_count[:, None].double(), r.rot_spread[:, None].double(),
@@ -645,6 +672,8 @@ def _log_hop(logger, fields, r, window, ms, last=None):
     if last is None:
         enc = r.pred_pose_enc[-1].tolist()  # (synchronises: the events are complete after it)
         row = dict(zip(STREAM_FIELDS, [r.frame_index, r.frame_index + window - 1] + enc + [ms]))
+        if r.track_src is not None:
+            row.update(zip(CARRY_FIELDS, _carry_counts(r)))
         positions = range(r.final) if r.final is not None else None
     else:
         row, positions = last, range(r.final, window)
@@ -657,7 +686,7 @@ def _log_hop(logger, fields, r, window, ms, last=None):
 
 
 def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, query_points=None, device="cuda",
-                anchor=None):
+                anchor=None, candidate_fn=None):
     """Online evaluation of one long sequence (opt-in: cfg.stream.enable must be true; train_fn /
     test_fn never call it). frames_iter yields uint8 [H, W, 3] frames in order (sequence_stream);
     each is cropped to `box` and resized / normalised on the device (crop_resize_normalize, the
@@ -670,7 +699,11 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
     anchor: the 5-tuple PoseStream takes. cfg.stream.fuse (default false; cfg.stream.fuse_weight: null
     or "score") turns pose fusion on: the CSV gains the FUSE_FIELDS columns, one row per frame whose
     fused pose is final (the first `stride` frames of each hop), and at the end of the stream one
-    flush writes the remaining frames of the last window. With fusion off the CSV is what it was."""
+    flush writes the remaining frames of the last window. With fusion off the CSV is what it was.
+    cfg.stream.carry (default false; with carry_cell, carry_border, carry_tracks, detect_every and the
+    required carry_min_score) turns track carry on (PoseStream carry=True): the queries come from the
+    carried tracks and candidate_fn (default: keypoint_candidates of the detectors), query_points must
+    be None, and the CSV gains the trailing columns survivors, born, padded. Off: the CSV is what it was."""
     from .data import crop_resize_normalize
     from .stream import PoseStream, keypoint_query
     if not _get(cfg, "stream.enable", False):
@@ -679,14 +712,18 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
     window = int(_get(cfg, "stream.window", _get(cfg, "seqlen", 16)))
     size = int(_get(cfg, "train.img_size", 512))
     query_fn = None
-    if query_points is None:
+    carry = _stream_carry(cfg, sp, sift, candidate_fn, device)
+    if query_points is None and not carry:
         sp = sp if sp is not None else _keypoint_init(cfg, device)
         query_fn = keypoint_query(sp, sift=sift, track_num=_get(cfg, "train.track_num", 512))
     mp = _get(cfg, "mixed_precision", "no")
     fuse, fuse_weight, anchor, fields = _stream_fuse(cfg, anchor)
     stream = PoseStream(model, window=window, stride=int(_get(cfg, "stream.stride", 1)),
                         capacity=_get(cfg, "stream.capacity", None), query_fn=query_fn, anchor=anchor,
-                        precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight)
+                        precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight,
+                        **carry)
+    if carry:
+        fields = tuple(fields) + CARRY_FIELDS
     logger = CsvLogger(csv_path, fields)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     hops, last = 0, None
@@ -705,7 +742,7 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
 
 
 def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_points=None, device="cuda",
-                     anchors=None):
+                     anchors=None, candidate_fn=None):
     """stream_eval for several sequences at a time (opt-in: cfg.stream.enable). `sequences` is an
     iterable of (name, frames_iter, box), each as stream_eval takes them; cfg.stream.streams
     (default 4) streams of one comet_amd.stream.StreamPool run side by side. Every free stream takes
@@ -716,7 +753,8 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
     events. -> {name: number of hops}. anchors: {sequence name: the 5-tuple PoseStream takes}.
     cfg.stream.fuse / fuse_weight as stream_eval: the fused columns, and a flush of its last window
     when a sequence ends (all hops of a push are fused by one launch; every anchor must then carry
-    one ratio and one dataset)."""
+    one ratio and one dataset). cfg.stream.carry and candidate_fn: as stream_eval (StreamPool
+    carry=True; a sequence that takes over a stream starts with fresh ids)."""
     from .data import crop_resize_normalize
     from .stream import StreamPool, keypoint_query
     if not _get(cfg, "stream.enable", False):
@@ -726,7 +764,8 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
     size = int(_get(cfg, "train.img_size", 512))
     S = int(_get(cfg, "stream.streams", 4))
     query_fn = None
-    if query_points is None:
+    carry = _stream_carry(cfg, sp, sift, candidate_fn, device)
+    if query_points is None and not carry:
         sp = sp if sp is not None else _keypoint_init(cfg, device)
         query_fn = keypoint_query(sp, sift=sift, track_num=_get(cfg, "train.track_num", 512))
     mp = _get(cfg, "mixed_precision", "no")
@@ -738,7 +777,10 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
     pool = StreamPool(model, streams=S, window=window, stride=int(_get(cfg, "stream.stride", 1)),
                       capacity=_get(cfg, "stream.capacity", None), query_fn=query_fn,
                       anchors=[default_anchor] * S if fuse else None,
-                      precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight)
+                      precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight,
+                      **carry)
+    if carry:
+        fields = tuple(fields) + CARRY_FIELDS
     lasts = {}  # stream id -> (last result, its row): flushed when the sequence ends
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     seqs = iter(sequences)

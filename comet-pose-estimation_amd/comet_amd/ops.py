@@ -694,6 +694,58 @@ def pose_fuse(enc, acc, slots, slots_host, fresh, fresh_host, first, first_host,
     return out
 
 
+class CarryOut(NamedTuple):
+    query: torch.Tensor  # [n, N, 2] f32 query points of the new windows
+    ids: torch.Tensor    # [n, N] int32 track ids (-1: a pad)
+    age: torch.Tensor    # [n, N] int32 hops the track has lived
+    src: torch.Tensor    # [n, N] int32: j carried, -1 - c born from candidate c, INT32_MIN + k pad copied from slot k
+    stats: torch.Tensor  # [n, 4] int32 (survivors, born, padded, dropped by the cell rule)
+
+
+def track_carry(tracks, score, ids, age, next_id, prev_valid, s, H, W, cell, border, min_score, cand=None, cand_n=None,
+                mask=None):
+    """comet_track_carry (include/comet_hip.h): the queries of n new windows from the previous
+    windows' tracks [n, T, N, 2] / score [n, T, N] (row s is read), ids / age [n, N] int32, the
+    candidates cand [n, M, 2] f32 with cand_n [n] int32 valid ones (None: no candidates) and
+    mask [n, H, W] uint8 (None: no mask), all in one launch -> CarryOut (new tensors; ids and age are
+    left as they are). next_id [n] int32 is advanced in place; prev_valid [n] int32."""
+    _req_cuda(tracks, score, ids, age, next_id, prev_valid, cand, cand_n, mask)
+    if tracks.dim() != 4 or tracks.shape[3] != 2 or tracks.dtype != torch.float32 or not tracks.is_contiguous():
+        raise L.CometHipError(f"track_carry: tracks must be a dense f32 [n, T, N, 2] tensor, got {tuple(tracks.shape)} "
+                              f"{tracks.dtype}")
+    n, T, N = tracks.shape[:3]
+    if score.shape != (n, T, N) or score.dtype != torch.float32 or not score.is_contiguous():
+        raise L.CometHipError("track_carry: score must be a dense f32 [n, T, N] tensor")
+    for name, t, shape in (("ids", ids, (n, N)), ("age", age, (n, N)), ("next_id", next_id, (n,)),
+                           ("prev_valid", prev_valid, (n,))):
+        if t.shape != shape or t.dtype != torch.int32 or not t.is_contiguous():
+            raise L.CometHipError(f"track_carry: {name} must be a dense int32 {list(shape)} tensor")
+    M = 0
+    if cand is not None:
+        if cand.dim() != 3 or cand.shape[0] != n or cand.shape[2] != 2 or cand.dtype != torch.float32 or not cand.is_contiguous():
+            raise L.CometHipError("track_carry: cand must be a dense f32 [n, M, 2] tensor")
+        M = cand.shape[1]
+        if cand_n is None or cand_n.shape != (n,) or cand_n.dtype != torch.int32 or not cand_n.is_contiguous():
+            raise L.CometHipError("track_carry: cand needs cand_n, a dense int32 [n] tensor")
+    if M == 0:
+        cand, cand_n = None, prev_valid  # (M == 0: cand_n is clamped to 0, whatever it holds)
+    if mask is not None and (mask.shape != (n, H, W) or mask.dtype != torch.uint8 or not mask.is_contiguous()):
+        raise L.CometHipError(f"track_carry: mask must be a dense uint8 [n, {H}, {W}] tensor")
+    dev = tracks.device
+    if any(t is not None and t.device != dev for t in (score, ids, age, next_id, prev_valid, cand, cand_n, mask)):
+        raise L.CometHipError("track_carry: every tensor must be on one device")
+    out = CarryOut(torch.empty(n, N, 2, device=dev), torch.empty(n, N, device=dev, dtype=torch.int32),
+                   torch.empty(n, N, device=dev, dtype=torch.int32), torch.empty(n, N, device=dev, dtype=torch.int32),
+                   torch.empty(n, 4, device=dev, dtype=torch.int32))
+    e0 = PROF.start()
+    L.check(L.load().comet_track_carry(_p(tracks), _p(score), _p(ids), _p(age), _p(mask), _p(cand), _p(cand_n),
+                                       _p(next_id), _p(prev_valid), n, T, N, M, int(s), int(H), int(W), int(cell),
+                                       int(border), float(min_score), *[_p(t) for t in out], stream()), "track_carry")
+    if e0 is not None:
+        PROF.stop(e0, "comet_track_carry", 0.0, float(n * (N * (12 + 8 + 8 + 20) + M * 16)))
+    return out
+
+
 def resize_bilinear_pool(x, oh, ow):
     """NHWC x [n, h, w, c] -> (y [n, oh, ow, c] bilinear, align_corners=True; its 2 x 2 average
     pool [n, oh // 2, ow // 2, c]) in one kernel: resize_bilinear + avgpool2_nhwc bit for bit."""

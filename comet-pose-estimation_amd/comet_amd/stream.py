@@ -16,13 +16,18 @@ them once per frame, keeps their outputs in device rings, and for every hop gath
   FuseSchedule   which hop is a stream's first, which window positions are new / final, host only
   PoseFuser      one fused pose per frame from the overlapping windows (comet_pose_fuse, one launch
                  per push); usable on its own with any [n, T, 7] encodings
+  CarrySchedule  which hop is a stream's first and on which hops the detector runs, host only
+  TrackCarry     persistent track ids: the next window's queries are this window's tracks on the frame
+                 that becomes first (comet_track_carry, one launch per push)
   keypoint_query query_fn from the SuperPoint / SIFT detectors of comet_amd.keypoints
+  keypoint_candidates  candidate_fn of the same detectors for carry=True: raw detections, no padding
 """
 import ctypes
 from typing import NamedTuple, Optional
 
 import torch
 
+from . import _lib as L
 from . import functional as F
 from . import ops
 
@@ -77,7 +82,7 @@ class RingSchedule:
         return self.stride
 
 
-class StreamResult(NamedTuple):
+class _StreamFields(NamedTuple):
     frame_index: int                   # global index of the window's first frame
     pred_pose_enc: torch.Tensor        # [T, 7], relative to the window's first frame
     pred_tracks: Optional[torch.Tensor]  # [T, N, 2]
@@ -91,6 +96,25 @@ class StreamResult(NamedTuple):
     rot_spread: Optional[torch.Tensor] = None    # [T] radians
     trans_spread: Optional[torch.Tensor] = None  # [T, 3], of (u, v, z)
     final: Optional[int] = None  # the leading positions whose fused pose will not change again
+
+
+class StreamResult(_StreamFields):
+    """The tuple above, followed by three fields that are attributes only (the tuple keeps its twelve
+    positions, so code that unpacks or slices a result sees what it saw): with carry=True the identity
+    of the track in every query slot (TrackCarry), else None."""
+    track_ids: Optional[torch.Tensor] = None  # [N] int32, -1: a pad
+    track_age: Optional[torch.Tensor] = None  # [N] int32 hops the track has lived
+    track_src: Optional[torch.Tensor] = None  # [N] int32: j carried, -1 - c born from candidate c, else a pad
+
+    def _replace(self, **kw):
+        r = super()._replace(**kw)
+        r.__dict__.update(self.__dict__)
+        return r
+
+    def with_tracks(self, track_ids, track_age, track_src):
+        r = self._replace()
+        r.track_ids, r.track_age, r.track_src = track_ids, track_age, track_src
+        return r
 
 
 class Anchor(NamedTuple):
@@ -285,6 +309,209 @@ def _fused_fields(out, b, final):
                 rot_spread=out.rot_spread[b], trans_spread=out.trans_spread[b], final=final)
 
 
+class CarrySchedule:
+    """The host-only arithmetic of track carry for `streams` streams of one window / stride: which hop
+    of a stream is its first (after construction or reset: nothing to carry, prev_valid = 0) and on
+    which hops the detector runs (hop index % detect_every == 0, so always on the first). The next
+    window's first frame must lie inside the current one: stride < window."""
+
+    def __init__(self, window, stride=1, streams=1, detect_every=1):
+        if stride < 1 or stride >= window:
+            raise ValueError(f"track carry needs 1 <= stride < window (stride {stride}, window {window}): the next "
+                             "window's first frame must lie inside the current window")
+        if streams < 1:
+            raise ValueError(f"at least 1 stream, got {streams}")
+        if detect_every < 1:
+            raise ValueError(f"detect_every must be at least 1, got {detect_every}")
+        self.window, self.stride, self.streams = int(window), int(stride), int(streams)
+        self.detect_every = int(detect_every)
+        self._hops = [0] * self.streams
+
+    def _id(self, stream):
+        s = int(stream)
+        if not 0 <= s < self.streams:
+            raise ValueError(f"unknown stream {s}: the schedule has streams 0 .. {self.streams - 1}")
+        return s
+
+    def reset(self, stream=None):
+        for s in (range(self.streams) if stream is None else [self._id(stream)]):
+            self._hops[s] = 0
+
+    def is_first(self, stream=0):
+        """Whether the next hop of the stream is its first (nothing is advanced)."""
+        return self._hops[self._id(stream)] == 0
+
+    def detects(self, stream=0):
+        """Whether the detector runs on the next hop of the stream (nothing is advanced)."""
+        return self._hops[self._id(stream)] % self.detect_every == 0
+
+    def hop(self, stream=0):
+        """Account for one hop of the stream -> (first, detect)."""
+        s = self._id(stream)
+        out = (self._hops[s] == 0, self._hops[s] % self.detect_every == 0)
+        self._hops[s] += 1
+        return out
+
+
+class TrackCarry:
+    """Persistent track identities across windows (DESIGN.md "Track carry").
+
+        carry = TrackCarry(window=T, stride=1, tracks=512, min_score=0.5)
+        out = carry.step([0], H, W, cands=[detections [M, 2]], masks=[None])   # ops.CarryOut, [1, N, ...]
+        ... run the model with out.query[0] as the window's query points ...
+        carry.update([0], pred_tracks [1, T, N, 2], pred_score [1, T, N])
+
+    Holds, per stream, the ids and ages of the N query slots and the id counter on the device, and a
+    reference to the stream's last pred_tracks / pred_score. step() is one comet_track_carry launch
+    for all the hops given (at most one per stream): a track that is still alive on the frame that
+    is now first (inside the frame and the mask, score >= min_score) and holds its grid cell keeps
+    its slot and id, free slots take candidates in detector order, the rest is padded (id -1). On a
+    hop where the detector does not run pass no candidates (CarrySchedule.detects)."""
+
+    _TABLES_MAX = 1024
+
+    def __init__(self, window, stride=1, streams=1, tracks=512, cell=8, border=0, min_score=None, detect_every=1):
+        self.sched = CarrySchedule(window, stride, streams, detect_every)
+        if min_score is None:
+            raise ValueError("track carry needs carry_min_score: the lowest pred_score a carried track may have "
+                             "(there is no default; DESIGN.md \"Track carry\" records the value the benchmark used)")
+        if not 1 <= int(tracks) <= L.CARRY_MAX_TRACKS:
+            raise ValueError(f"carry_tracks must lie in [1, {L.CARRY_MAX_TRACKS}], got {tracks}")
+        if int(cell) < 1 or int(border) < 0:
+            raise ValueError(f"carry_cell must be at least 1 and carry_border at least 0, got {cell} and {border}")
+        self.tracks, self.cell, self.border, self.min_score = int(tracks), int(cell), int(border), float(min_score)
+        self.device = None
+        self._last = {}  # stream -> (pred_tracks [n, T, N, 2], pred_score [n, T, N], row)
+
+    def _ensure(self, dev):
+        if self.device == dev:
+            return
+        S, N, T = self.sched.streams, self.tracks, self.sched.window
+        self.device = dev
+        self.ids = torch.full((S, N), -1, dtype=torch.int32, device=dev)
+        self.age = torch.zeros(S, N, dtype=torch.int32, device=dev)
+        self.next_id = torch.zeros(S, dtype=torch.int32, device=dev)
+        self._blank = (torch.zeros(T, N, 2, device=dev), torch.zeros(T, N, device=dev))
+        self._tables, self._last = {}, {}
+        self.sched.reset()
+
+    def _table(self, values, dtype=torch.int32):
+        key = (dtype, tuple(values))
+        hit = self._tables.get(key)
+        if hit is None:
+            if len(self._tables) >= self._TABLES_MAX:
+                self._tables.clear()
+            hit = self._tables[key] = torch.tensor(key[1], dtype=dtype, device=self.device)
+        return hit
+
+    def reset(self, stream=None):
+        """The next hop of `stream` (default: of every stream) is a first hop again: no track is
+        carried into it and its ids start at 0."""
+        self.sched.reset(stream)
+        if self.device is None:
+            return
+        if stream is None:
+            self._last.clear()
+            self.next_id.zero_()
+        else:
+            self._last.pop(int(stream), None)
+            self.next_id[int(stream)] = 0
+
+    def detects(self, stream=0):
+        return self.sched.detects(stream)
+
+    def _previous(self, sids):
+        """pred_tracks [n, T, N, 2] and pred_score [n, T, N] of the streams' last windows: the batched
+        outputs themselves when the same streams ran as one batch, else stacked."""
+        refs = [None if self.sched.is_first(s) else self._last.get(s) for s in sids]
+        r0 = refs[0]
+        if r0 is not None and r0[0].shape[0] == len(sids) and all(
+                r is not None and r[0] is r0[0] and r[2] == i for i, r in enumerate(refs)):
+            return r0[0], r0[1]
+        rows = [self._blank if r is None else (r[0][r[2]], r[1][r[2]]) for r in refs]
+        if len(rows) == 1:
+            return rows[0][0][None], rows[0][1][None]
+        return torch.stack([t for t, _ in rows]), torch.stack([s for _, s in rows])
+
+    def step(self, sids, H, W, cands=None, masks=None):
+        """The queries of the next hop of every stream in `sids` (distinct) -> ops.CarryOut [n, N, ...].
+        cands: per hop the detections [M, 2] in detector order, or None; masks: per hop [H, W] bool /
+        uint8 or None (no mask at all when every entry is None)."""
+        sids = [self.sched._id(s) for s in sids]
+        n = len(sids)
+        if n == 0 or len(set(sids)) != n:
+            raise ValueError(f"step takes at least one hop and one hop per stream, got the streams {sids}")
+        cands = list(cands) if cands is not None else [None] * n
+        masks = list(masks) if masks is not None else [None] * n
+        if len(cands) != n or len(masks) != n:
+            raise ValueError(f"{n} hops need {n} candidate sets and masks")
+        dev = next((t.device for t in cands + masks if t is not None), self.device)
+        if dev is None:
+            raise ValueError("the first step needs a candidate set or a mask (they give the device)")
+        self._ensure(dev)
+        N, S = self.tracks, self.sched.streams
+        tr, sc = self._previous(sids)
+        prev_valid = self._table([0 if self.sched.is_first(s) else 1 for s in sids])
+        # candidates, padded to a common M
+        cands = [None if c is None else c.to(dev, torch.float32).reshape(-1, 2)[:L.CARRY_MAX_CANDIDATES] for c in cands]
+        counts = [0 if c is None else c.shape[0] for c in cands]
+        M = max(counts)
+        cand = cand_n = None
+        if M > 0:
+            cand_n = self._table(counts)
+            if n == 1:
+                cand = cands[0].contiguous()[None]
+            else:
+                cand = torch.zeros(n, M, 2, device=dev)
+                for b, c in enumerate(cands):
+                    if c is not None:
+                        cand[b, :counts[b]] = c
+        mask = None
+        if any(m is not None for m in masks):
+            ms = [torch.ones(H, W, dtype=torch.uint8, device=dev) if m is None else
+                  (m if m.dtype in (torch.bool, torch.uint8) else m != 0).to(dev).contiguous().view(torch.uint8)
+                  for m in masks]
+            mask = ms[0][None] if n == 1 else torch.stack(ms)
+        whole = sids == list(range(S))
+        if whole:
+            ids, age, next_id = self.ids, self.age, self.next_id
+        else:
+            idx = self._table(sids, torch.int64)
+            ids, age, next_id = self.ids.index_select(0, idx), self.age.index_select(0, idx), self.next_id.index_select(0, idx)
+        out = ops.track_carry(tr, sc, ids, age, next_id, prev_valid, self.sched.stride, H, W, self.cell, self.border,
+                              self.min_score, cand, cand_n, mask)
+        if whole:
+            self.ids, self.age = out.ids, out.age  # (new tensors: results handed out earlier stay as they were)
+        else:
+            # (out of place: a whole-batch step's outputs are the state and are also views of results handed out)
+            self.ids = self.ids.index_copy(0, idx, out.ids)
+            self.age = self.age.index_copy(0, idx, out.age)
+            self.next_id.index_copy_(0, idx, next_id)
+        for s in sids:  # (only a launch that went out advances the schedule)
+            self.sched.hop(s)
+        return out
+
+    def update(self, sids, pred_tracks, pred_score):
+        """Keep the windows' outputs for the next step: pred_tracks [n, T, N, 2], pred_score [n, T, N]
+        of the hops of `sids`, in their order."""
+        if pred_tracks is None or pred_score is None:
+            raise RuntimeError("track carry needs the model's pred_tracks and pred_score outputs")
+        tr, sc = pred_tracks.float().contiguous(), pred_score.float().contiguous()
+        for b, s in enumerate(sids):
+            self._last[int(s)] = (tr, sc, b)
+
+
+def _check_carry(carry, candidate_fn, query_points=None):
+    if carry and candidate_fn is None:
+        raise ValueError("carry=True needs a candidate_fn (keypoint_candidates): free slots take its detections")
+    if carry and query_points is not None:
+        raise ValueError("explicit query_points together with carry=True: the carried tracks are the query points")
+
+
+def _carry_fields(co, b):
+    return co.ids[b], co.age[b], co.src[b]
+
+
 class PoseStream:
     """Sliding-window pose estimation over a frame stream.
 
@@ -322,13 +549,33 @@ class PoseStream:
     vanishes as stride approaches window / 2, where the chained frame has a single hypothesis.
     _decode_chained is not called when fuse is on; with fuse=False nothing changes.
 
+    carry=True (needs stride < window, a candidate_fn and carry_min_score; query_points / query_fn are
+    then not used) keeps tracks alive from window to window (TrackCarry, DESIGN.md "Track carry"): every
+    window has carry_tracks query slots; a track whose refined position on the frame that becomes the
+    next window's first frame is inside the frame (carry_border), inside mask_fn(frame) -> [H, W] bool
+    when given, has pred_score >= carry_min_score and holds its carry_cell x carry_cell pixel cell
+    keeps its slot and id, and that position is the next query. Free slots take candidate_fn(frame)
+    -> [M, 2] (keypoint_candidates) in detector order on the hops where the detector runs (every
+    detect_every-th hop of the stream, always the first), the rest is padded. Results then carry
+    track_ids, track_age and track_src. carry_min_score has no default: the model was trained with
+    detector keypoints on frame 0, and what carried queries do to pose accuracy is unmeasured beyond
+    DESIGN.md "Track carry" (whose benchmark used 0.0). With carry=False nothing changes.
+
     One stream (batch 1). The model is used as is (its eval / train mode included)."""
 
     def __init__(self, model, window, stride=1, capacity=None, query_fn=None, anchor=None, precision=None,
-                 fuse=False, fuse_weight=None):
+                 fuse=False, fuse_weight=None, carry=False, carry_tracks=512, carry_cell=8, carry_border=0,
+                 carry_min_score=None, detect_every=1, candidate_fn=None, mask_fn=None):
         self.model = model
         self.sched = RingSchedule(window, stride, capacity)
         self.query_fn = query_fn
+        self.carry, self.candidate_fn, self.mask_fn = bool(carry), candidate_fn, mask_fn
+        self._carry = None
+        if self.carry:
+            self.sched.chain_index()  # raises unless stride < window
+            _check_carry(True, candidate_fn)
+            self._carry = TrackCarry(window, stride, 1, carry_tracks, carry_cell, carry_border, carry_min_score,
+                                     detect_every)
         self.precision = precision if precision is not None else _model_precision(model)
         _check_fuse(fuse, fuse_weight, anchor is not None)
         self.fuse, self.fuse_weight = bool(fuse), fuse_weight
@@ -348,6 +595,8 @@ class PoseStream:
         self._ref = None     # (R [4] f32, T_uvz [3] f32) the next hop is decoded against
         if self._fuser is not None:
             self._fuser.reset()
+        if self._carry is not None:
+            self._carry.reset()
 
     # -- ring -------------------------------------------------------------------------------------
     @staticmethod
@@ -395,7 +644,14 @@ class PoseStream:
     def _hop(self, hop, query_points):
         T = self.sched.window
         cache = self._gather(hop.head)
-        if query_points is None:
+        co = None
+        if self.carry:
+            frame = cache.refine_frames[0, 0]
+            cand = self.candidate_fn(frame) if self._carry.detects(0) else None
+            mask = self.mask_fn(frame) if self.mask_fn is not None else None
+            co = self._carry.step([0], frame.shape[-2], frame.shape[-1], [cand], [mask])
+            query_points = co.query[0]
+        elif query_points is None:
             query_points = self.query_fn(cache.refine_frames[0, 0])
         q = query_points.to(self._tables.device, torch.float32)
         tracks = q[None, None].expand(1, T, -1, 2)
@@ -406,6 +662,9 @@ class PoseStream:
         sc = out.get("_track_predictions", {}).get("pred_score")
         R = Tx = None
         res = StreamResult(hop.frame_index, enc, None if tr is None else tr[0], None if sc is None else sc[0])
+        if co is not None:
+            self._carry.update([0], tr, sc)
+            res = res.with_tracks(*_carry_fields(co, 0))
         if self.fuse:
             w = _score_weights(sc) if self.fuse_weight == "score" else None
             return res._replace(**_fused_fields(self._fuser.fuse(enc, [(0, hop)], w), 0, self._fuser.sched.final))
@@ -424,7 +683,8 @@ class PoseStream:
         hw = tuple(frames.shape[-2:])
         if self._hw is not None and hw != self._hw:
             raise ValueError(f"frame size changed from {self._hw} to {hw}; reset() starts a new stream")
-        if query_points is None and self.query_fn is None:
+        _check_carry(self.carry, self.candidate_fn, query_points)
+        if query_points is None and self.query_fn is None and not self.carry:
             raise ValueError("no query source: pass query_points to push() or query_fn to PoseStream")
         results = []
         with F.precision(self.precision):
@@ -551,7 +811,9 @@ class StreamPool:
     code, so for the same pred_pose_enc the same bits). fuse / fuse_weight: as PoseStream's; all the
     hops due in a push, of every query-count group, are fused by one comet_pose_fuse launch. With
     fuse=True every anchor must carry the same ratio and dataset (one launch takes one ratio and one
-    set of intrinsics).
+    set of intrinsics). carry / carry_* / detect_every / candidate_fn / mask_fn: as PoseStream's; every
+    carried hop has carry_tracks queries, so the hops due in a push are one group, and one
+    comet_track_carry launch serves them all; reset(stream) restarts that stream's ids and ages.
 
     push() -> [(stream id, StreamResult)] ordered by stream id. The tensors of a result are views
     of the batched outputs. The model is used as is (its eval / train mode included)."""
@@ -559,10 +821,18 @@ class StreamPool:
     _TABLES_MAX = 1024  # cached device slot tables (periodic in capacity for streams in phase)
 
     def __init__(self, model, streams, window, stride=1, capacity=None, query_fn=None, anchors=None, precision=None,
-                 fuse=False, fuse_weight=None):
+                 fuse=False, fuse_weight=None, carry=False, carry_tracks=512, carry_cell=8, carry_border=0,
+                 carry_min_score=None, detect_every=1, candidate_fn=None, mask_fn=None):
         self.model = model
         self.sched = PoolSchedule(streams, window, stride, capacity)
         self.query_fn = query_fn
+        self.carry, self.candidate_fn, self.mask_fn = bool(carry), candidate_fn, mask_fn
+        self._carry = None
+        if self.carry:
+            self.sched.scheds[0].chain_index()  # raises unless stride < window
+            _check_carry(True, candidate_fn)
+            self._carry = TrackCarry(window, stride, streams, carry_tracks, carry_cell, carry_border, carry_min_score,
+                                     detect_every)
         self.precision = precision if precision is not None else _model_precision(model)
         _check_fuse(fuse, fuse_weight, anchors is not None)
         self.fuse, self.fuse_weight = bool(fuse), fuse_weight
@@ -607,6 +877,8 @@ class StreamPool:
             self.anchors[int(stream)] = a
         if self._fuser is not None:
             self._fuser.reset(stream)
+        if self._carry is not None:
+            self._carry.reset(stream)
         if stream is None:
             self._rings = self._wins = self._hw = self._dev = None
             self._tables = {}
@@ -662,10 +934,18 @@ class StreamPool:
         return R, Tx
 
     # -- hops -------------------------------------------------------------------------------------
-    def _hops(self, hops, qs, pos, fused=None):
+    def _carried(self, hops):
+        """carry=True: the queries of all the hops due, one comet_track_carry launch -> ops.CarryOut."""
+        firsts = [self._rings[1][self.sched.slot(sid, hop.frame_index)] for sid, hop in hops]
+        cands = [self.candidate_fn(f) if self._carry.detects(sid) else None for f, (sid, _) in zip(firsts, hops)]
+        masks = [self.mask_fn(f) if self.mask_fn is not None else None for f in firsts]
+        return self._carry.step([sid for sid, _ in hops], self._hw[0], self._hw[1], cands, masks)
+
+    def _hops(self, hops, qs, pos, fused=None, co=None):
         """The hops hops[i], i in pos (all with N query points) as one batched call ->
         [(stream, StreamResult)] in the order of pos. fused (fuse=True): a list that takes the
-        group's (pred_pose_enc, pred_score); the absolute poses are then left to _fuse."""
+        group's (pred_pose_enc, pred_score); the absolute poses are then left to _fuse. co
+        (carry=True): the ops.CarryOut whose rows are the hops' queries (pos is then every hop)."""
         from .models.E2Epose2 import FrameCache
         T, n = self.sched.window, len(pos)
         table, table_host = self._table(self.sched.table([hops[i] for i in pos]))
@@ -674,7 +954,7 @@ class StreamPool:
         fm, fr, tok = wins
         cache = FrameCache(fmaps=None if fm is None else fm.view(n, T, *fm.shape[1:]),
                            refine_frames=fr.view(n, T, *fr.shape[1:]), tokens=tok)
-        tracks = torch.stack([qs[i] for i in pos])[:, None].expand(n, T, -1, 2)
+        tracks = (co.query if co is not None else torch.stack([qs[i] for i in pos]))[:, None].expand(n, T, -1, 2)
         # (with a frame_cache the model reads only the shape of its image argument)
         out = self.model.forward_all(cache.refine_frames, training=False, tracks=tracks, frame_cache=cache)
         enc = out["pred_pose_enc"]  # [n * T, 7]
@@ -683,6 +963,8 @@ class StreamPool:
         results = []
         if fused is not None:
             fused.append((enc, sc))
+        if co is not None:
+            self._carry.update([hops[i][0] for i in pos], tr, sc)
         for b, i in enumerate(pos):
             sid, hop = hops[i]
             e = enc[b * T:(b + 1) * T]
@@ -691,6 +973,8 @@ class StreamPool:
                 R, Tx = self._decode(sid, e, T)
             results.append((sid, StreamResult(hop.frame_index, e, None if tr is None else tr[b],
                                               None if sc is None else sc[b], R, Tx)))
+            if co is not None:
+                results[-1] = (sid, results[-1][1].with_tracks(*_carry_fields(co, b)))
         return results
 
     def _fuse(self, hops, results, fused):
@@ -717,7 +1001,8 @@ class StreamPool:
         hw = tuple(frames.shape[-2:])
         if self._hw is not None and hw != self._hw:
             raise ValueError(f"frame size changed from {self._hw} to {hw}; reset() starts new streams")
-        if self.query_fn is None:
+        _check_carry(self.carry, self.candidate_fn, query_points)
+        if self.query_fn is None and not self.carry:
             if query_points is None:
                 raise ValueError("no query source: pass query_points to push() or query_fn to StreamPool")
             if isinstance(query_points, dict):
@@ -735,11 +1020,15 @@ class StreamPool:
             ops.ring_scatter([(t.contiguous(), r) for t, r in zip(per, self._rings) if r is not None],
                              slot_table, slot_host)
             if hops:
-                qs = [self._query(sid, hop, query_points) for sid, hop in hops]
                 fused, order = ([] if self.fuse else None), []
-                for _, pos in self.sched.group([q.shape[0] for q in qs]):
-                    results += self._hops(hops, qs, pos, fused)
-                    order += pos
+                if self.carry:  # every hop has carry_tracks queries: one group
+                    order = list(range(len(hops)))
+                    results = self._hops(hops, None, order, fused, self._carried(hops))
+                else:
+                    qs = [self._query(sid, hop, query_points) for sid, hop in hops]
+                    for _, pos in self.sched.group([q.shape[0] for q in qs]):
+                        results += self._hops(hops, qs, pos, fused)
+                        order += pos
                 if self.fuse:
                     results = self._fuse([hops[i] for i in order], results, fused)
         return sorted(results, key=lambda r: r[0])
@@ -760,3 +1049,16 @@ def keypoint_query(sp, sift=None, mask_fn=None, track_num=512, min_required=256)
         mask = torch.ones(H, W, dtype=torch.bool, device=frame.device) if mask_fn is None else mask_fn(frame).bool()
         return filter_and_pad(pts, mask, min(min_required, track_num), track_num)
     return query
+
+
+def keypoint_candidates(sp, sift=None):
+    """candidate_fn for carry=True from the detectors of comet_amd.keypoints: the raw detections of
+    SuperPoint.extract (then SIFT.extract when given) on a frame [3, H, W] -> [M, 2] in detector
+    order, neither filtered nor padded: comet_track_carry applies the mask, the border and the
+    one-per-cell rule and pads to the fixed track count."""
+    def candidates(frame):
+        pts = sp.extract(frame)["keypoints"][0]
+        if sift is not None:
+            pts = torch.cat([pts, sift.extract(frame)["keypoints"][0]], 0)
+        return pts
+    return candidates

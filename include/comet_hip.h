@@ -568,6 +568,56 @@ int comet_pose_fuse(const float* enc, const int32_t* slots, const int32_t* slots
                     int32_t* count_out, float* rot_spread, float* trans_spread, float* hyp_R,
                     double* hyp_T, void* stream);
 
+/* comet_track_carry (DESIGN.md "Track carry"): the query points of the n hops of a push from the
+ *   previous windows' tracks, one launch, one workgroup of 256 threads per hop (no communication
+ *   between workgroups, no global atomics; every selection is order-independent, so the result is
+ *   deterministic). Per hop b:
+ *     tracks [n, T, N, 2] f32, score [n, T, N] f32: pred_tracks / pred_score of the previous window
+ *       (score as the model returns it, larger is better); only row s (= stride) is read.
+ *     ids, age [n, N] int32: the previous ids and ages; id < 0 marks a slot that holds no track.
+ *     mask [n, H, W] uint8 or NULL: object mask of the new first frame.
+ *     cand [n, M, 2] f32 (NULL only when M == 0): candidates in detector order, best first;
+ *     cand_n [n] int32 on the device: valid candidates of the hop (clamped to [0, M]).
+ *     next_id [n] int32: the hop's id counter, read and written.
+ *     prev_valid [n] int32: 0 on a stream's first hop -- tracks and score are not read, every slot
+ *       counts as dead.
+ *   Rules:
+ *   1. Alive: x and y finite; border <= x <= W - 1 - border and border <= y <= H - 1 - border; with
+ *      a mask, mask[clamp(rint(y), 0, H - 1), clamp(rint(x), 0, W - 1)] != 0 (rint: round half to
+ *      even, the indexing of filter_and_pad). A previous track also needs id >= 0 and
+ *      score[b, s, j] >= min_score (a NaN score is dead).
+ *   2. One track per cell: cell = (floor(x / cell), floor(y / cell)) in f32 on a grid of
+ *      ceil(W / cell) x ceil(H / cell). Every alive point posts a 32-bit key with an LDS atomicMin:
+ *      a previous track (2^19 - 1 - clamp(age, 0, 2^19 - 1)) << 12 | j (bit 31 clear), a candidate
+ *      1 << 31 | c. A point is kept iff its key is its cell's minimum: a track beats any candidate,
+ *      among tracks the older wins, then the lower slot; among candidates the lower index.
+ *   3. A kept track stays in slot j with its id; age_out = age + 1 (saturating at INT32_MAX, a
+ *      negative age counts as 0); query[b, j] = tracks[b, s, j] bit for bit; src = j.
+ *   4. Births: the r-th free slot (ascending j) takes the r-th kept candidate (ascending c), ranks
+ *      by exclusive prefix sums over the workgroup in chunks of 256 with a carry: query = cand[b, c],
+ *      id = next_id + r, age = 0, src = -1 - c. next_id grows by the number born.
+ *   5. Pads: with the live slots (kept and born) l_0 < ... < l_{L-1}, the r-th slot still free
+ *      (ascending j) copies the query of l_{r mod L}: id = -1, age = 0, src = INT32_MIN + l. If
+ *      L == 0 it is a lattice point, g = ceil(sqrt(N)), in f32 evaluated left to right
+ *        x = ((float)(r % g) + 0.5f) * (float)W / (float)g,  y = ((float)(r / g) + 0.5f) * (float)H / (float)g,
+ *      id = -1, src = INT32_MIN. A pad has id < 0, so the next hop treats its slot as free.
+ *   Outputs: query [n, N, 2] f32; ids_out, age_out, src [n, N] int32; stats [n, 4] int32 =
+ *   (survivors, born, padded, alive tracks dropped by rule 2). ids_out == ids and age_out == age
+ *   (in place) is allowed: a slot is read and written by one thread, reads first.
+ *   LDS: 32 KiB of keys (8192 cells) + 16 KiB rank list + 4 KiB slot states, static.
+ *   COMET_EINVAL before anything is launched: a null pointer (mask may be null; cand only when
+ *   M == 0), n < 1, N outside [1, 4096], M outside [0, 65536], s outside [1, T - 1], H or W < 1,
+ *   cell < 1, border < 0, more than 8192 grid cells, tracks / cand / query not 8-B aligned. Slot and
+ *   candidate indices are range-checked in the kernel before they address memory. */
+#define COMET_CARRY_MAX_TRACKS 4096
+#define COMET_CARRY_MAX_CANDIDATES 65536
+#define COMET_CARRY_MAX_CELLS 8192
+int comet_track_carry(const float* tracks, const float* score, const int32_t* ids, const int32_t* age,
+                      const uint8_t* mask, const float* cand, const int32_t* cand_n, int32_t* next_id,
+                      const int32_t* prev_valid, int n, int T, int N, int M, int s, int H, int W, int cell,
+                      int border, float min_score, float* query, int32_t* ids_out, int32_t* age_out,
+                      int32_t* src, int32_t* stats, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Debug support (bounds asserts and a NaN / Inf check mode).
  * comet_count_nonfinite: adds the number of NaN / Inf elements of x (n elements, dtype) to

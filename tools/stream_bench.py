@@ -28,7 +28,19 @@ Two anchored streams (with --streams: two anchored pools of S streams) take the 
   (a) fuse on   one comet_pose_fuse launch per push for the absolute poses;
   (b) fuse off  two comet_pose_decode launches and the torch arithmetic of _decode_chained per hop;
   (c) kernel    the comet_pose_fuse launch of a push alone, on a scratch PoseFuser.
-(a) and (b) alternate push by push in one process; device events, medians and minima."""
+(a) and (b) alternate push by push in one process; device events, medians and minima.
+
+--carry [--detect-every K] [--min-score V]: track carry (comet_track_carry, DESIGN.md "Track carry")
+against the detector on every hop. Needs the SuperPoint weights of cfg (as loop.stream_eval does).
+Three PoseStream objects take the same frames, alternating hop by hop in one process:
+  (a) query_fn  query_fn = keypoint_query(sp): SuperPoint + filter_and_pad on every hop (the path before);
+  (b) carry 1   carry=True, detect_every=1: SuperPoint on every hop, no filter_and_pad;
+  (c) carry K   carry=True, detect_every=K (default 4);
+  (d) kernel    the comet_track_carry launch of (b)'s hop alone (20 back-to-back launches / 20).
+Also per timed hop of (b) and (c): survivors, born, padded and the mean age, and the largest
+pred_pose_enc difference between (a) and (b) on the same windows (a difference between two query
+sets, not an error against ground truth). Random-init weights and N(0,1) frames: the tracks say little
+about real imagery."""
 import argparse
 import json
 import os
@@ -153,6 +165,71 @@ def fuse_bench(model, n_streams, args, dev):
         "data": "synthetic (N(0,1) frames, U[0,S-1] query points); random-init weights"}), flush=True)
 
 
+def carry_bench(model, args, dev, cfg):
+    from comet_amd import loop, ops
+    from comet_amd.stream import PoseStream, keypoint_candidates, keypoint_query
+    T, S, N = args.frames, args.image, args.tracks
+    g = torch.Generator(device=dev).manual_seed(1)
+    total = T + args.warmup + args.hops - 1
+    frames = torch.randn(total, 3, S, S, device=dev, generator=g)
+    sp = loop._keypoint_init(cfg, dev)
+    kw = dict(window=T, stride=1, precision=torch.bfloat16)
+    ckw = dict(kw, carry=True, carry_tracks=N, carry_cell=args.cell, carry_min_score=args.min_score,
+               candidate_fn=keypoint_candidates(sp))
+    objs = {"query_fn": PoseStream(model, query_fn=keypoint_query(sp, track_num=N, min_required=N), **kw),
+            "carry_1": PoseStream(model, detect_every=1, **ckw),
+            "carry_k": PoseStream(model, detect_every=args.detect_every, **ckw)}
+    names = list(objs)
+    for o in objs.values():
+        assert o.push(frames[:T - 1]) == []
+    times = {k: [] for k in names}
+    stats = {k: [] for k in names[1:]}
+    tk, err = [], 0.0
+    for j in range(args.warmup + args.hops):
+        i = j + T - 1
+        res = {}
+        for k in names[j % 3:] + names[:j % 3]:  # (no path always runs first)
+            ms, out = _timed(lambda: objs[k].push(frames[i]))
+            assert len(out) == 1 and out[0].frame_index == j
+            res[k] = (ms, out[0])
+        tc = objs["carry_1"]._carry
+        cand = objs["carry_1"].candidate_fn(frames[j]).float().contiguous()[None]
+        cn = torch.tensor([cand.shape[1]], dtype=torch.int32, device=dev)
+        pv = torch.ones(1, dtype=torch.int32, device=dev)
+        r = res["carry_1"][1]
+        nid = tc.next_id.clone()
+        ms_k, _ = _timed(lambda: [ops.track_carry(r.pred_tracks[None], r.pred_score[None].float(), tc.ids, tc.age, nid, pv, 1,
+                                                  S, S, args.cell, 0, args.min_score, cand, cn) for _ in range(GATHER_REPS)])
+        if j >= args.warmup:
+            for k in names:
+                times[k].append(res[k][0])
+            tk.append(ms_k / GATHER_REPS)
+            err = max(err, float((res["query_fn"][1].pred_pose_enc - res["carry_1"][1].pred_pose_enc).abs().max()))
+            for k in names[1:]:
+                rr = res[k][1]
+                sv, bn, pd = loop._carry_counts(rr)
+                live = rr.track_ids >= 0
+                stats[k].append((sv, bn, pd, float(rr.track_age[live].float().mean()) if bool(live.any()) else 0.0))
+    out = {"metric": f"ms per hop, track carry against a detector + filter_and_pad on every hop, PoseStream, T={T} {S}^2 "
+                     f"N={N}, bf16, stride 1", "detect_every": args.detect_every, "carry_min_score": args.min_score,
+           "carry_cell": args.cell}
+    for k in names:
+        out[f"{k}_ms"] = round(statistics.median(times[k]), 3)
+        out[f"min_{k}_ms"] = round(min(times[k]), 3)
+    out["track_carry_ms"] = round(statistics.median(tk), 4)
+    out["min_track_carry_ms"] = round(min(tk), 4)
+    out["track_carry_timing"] = f"device events around {GATHER_REPS} back-to-back launches / {GATHER_REPS}, median over the hops"
+    for k in names[1:]:
+        cols = list(zip(*stats[k]))
+        out[f"{k}_per_hop_mean"] = dict(zip(("survivors", "born", "padded", "mean_age"),
+                                            [round(statistics.mean(c), 2) for c in cols]))
+        out[f"{k}_per_hop_min_max_survivors"] = [min(cols[0]), max(cols[0])]
+    out.update({"hops": args.hops, "warmup": args.warmup, "max_abs_pose_enc_diff_query_fn_vs_carry_1": err,
+                "pose_enc_diff_note": "a difference between two query sets on the same windows, not an error against ground truth",
+                "data": "synthetic (N(0,1) frames); random-init weights: the track statistics say little about real imagery"})
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16, help="window length T")
@@ -164,6 +241,10 @@ def main():
                     help="comma-separated stream counts: time StreamPool against that many separate PoseStream objects")
     ap.add_argument("--fuse", action="store_true",
                     help="time pose fusion on against off (PoseStream, or StreamPool with --streams)")
+    ap.add_argument("--carry", action="store_true", help="time track carry against the detector on every hop")
+    ap.add_argument("--detect-every", type=int, default=4, help="--carry: the detector period of the third stream")
+    ap.add_argument("--min-score", type=float, default=0.0, help="--carry: carry_min_score")
+    ap.add_argument("--cell", type=int, default=8, help="--carry: carry_cell")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         print("stream_bench: no GPU", file=sys.stderr)
@@ -176,6 +257,9 @@ def main():
     cfg = load_config()
     torch.manual_seed(0)
     model = instantiate(cfg.MODEL, _recursive_=False, cfg=cfg).to(dev).eval()
+    if args.carry:
+        carry_bench(model, args, dev, cfg)
+        return 0
     if args.fuse:
         for n_streams in ([0] if args.streams is None else [int(v) for v in args.streams.split(",")]):
             fuse_bench(model, n_streams, args, dev)
