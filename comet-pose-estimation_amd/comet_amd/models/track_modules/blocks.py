@@ -9,6 +9,8 @@ im2col + MFMA GEMM, InstanceNorm/ReLU/residual tails are fused kernels.
   EfficientUpdateFormer blocks.py:205-348 (time / virtual-track space attention)
 """
 
+import os
+
 import torch
 import torch.nn as nn
 
@@ -86,6 +88,26 @@ class ShallowEncoder(nn.Module):
         self.in_planes = dim
         return ResidualBlock(self.in_planes, dim, self.norm_fn, stride=stride)
 
+    def _front(self, x):
+        """(x, tmp1, tmp2) from the fused front kernel when the input is eligible (bf16 compute, bf16
+        31 x 31 x 8 patches, the encoder's own geometry), else None: the caller runs the separate
+        launches. COMET_SHALLOW_FRONT=0 (read per call) forces the separate launches for A/B runs."""
+        if os.environ.get("COMET_SHALLOW_FRONT", "1") == "0" or F.compute_dtype() != torch.bfloat16:
+            return None
+        if x.dtype != torch.bfloat16 or x.dim() != 4 or tuple(x.shape[1:]) != (31, 31, 8):
+            return None
+        l1, l2 = self.layer1, self.layer2
+        if l1.downsample is None or l2.downsample is None or (l1.stride, l2.stride) != (2, 2):
+            return None
+        convs = (self.conv1, l1.conv1, l1.conv2, l1.downsample[0], l2.conv1, l2.conv2, l2.downsample[0])
+        if any(cv.bias is None for cv in convs) or self.conv1.weight.shape[1] > 8:
+            return None
+        ws = [F.wcast_conv(cv.weight, cin_pad=8 if cv is self.conv1 else None) for cv in convs]
+        bs = [cv.bias for cv in convs]
+        if not ops.shallow_front_ok(x, ws, bs):
+            return None
+        return ops.shallow_front(x, ws, bs)
+
     @torch.no_grad()
     def forward(self, x, with_pool=False):
         """x NHWC [n, P, P, 3] -> NHWC [n, P/stride, P/stride, 32] (with_pool: also its 2x2 average
@@ -93,13 +115,19 @@ class ShallowEncoder(nn.Module):
         the resize-and-adds, conv2, the residual, the up-sampling and the pools in one kernel,
         comet_conv1x1_resize_pool_nhwc)."""
         _, H, W, _ = x.shape
-        x = ops.instnorm_nhwc(conv2d_nhwc(x, self.conv1, 2, 1), relu=True)
+        front = self._front(x)
+        if front is not None:
+            # conv1 + norm + relu and both residual layers in one kernel (comet_shallow_front_nhwc)
+            x, tmp1, tmp2 = front
+        else:
+            x = ops.instnorm_nhwc(conv2d_nhwc(x, self.conv1, 2, 1), relu=True)
         h, w = x.shape[1], x.shape[2]
         n, _, _, c = x.shape
         oh, ow = H // self.stride, W // self.stride
         w2 = F.wcast(self.conv2.weight.reshape(c, c))
-        tmp1 = self.layer1(x)
-        tmp2 = self.layer2(tmp1)  # (layer2 reads layer1's output, not x: the two adds below can wait)
+        if front is None:
+            tmp1 = self.layer1(x)
+            tmp2 = self.layer2(tmp1)  # (layer2 reads layer1's output, not x: the two adds below can wait)
         if with_pool and ops.conv1x1_resize_pool_ok(x, w2, self.conv2.bias, tmp1, tmp2):
             # both resize-and-adds, conv2 (1x1) + residual, the up-sampling and the pyramid's pools
             # in one kernel (the sums and the conv2 output never in HBM)

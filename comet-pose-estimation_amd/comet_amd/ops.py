@@ -787,6 +787,46 @@ def conv1x1_resize_pool_ok(x, w, b, *ups):
     return ok
 
 
+_SHALLOW_FRONT_K = (72, 288, 288, 32, 288, 288, 32)  # kh * kw * cin of the seven convolutions, in call order
+
+
+def shallow_front(patches, ws, bs, eps=1e-5):
+    """The fine ShallowEncoder's front in one kernel (comet_shallow_front_nhwc): patches
+    [n, 31, 31, 8] bf16 -> x [n, 16, 16, 32], tmp1 [n, 8, 8, 32], tmp2 [n, 4, 4, 32], the unfused
+    conv2d_nhwc + instnorm_nhwc calls bit for bit. ws / bs: the weights ([32, kh*kw*cin] bf16,
+    columns (ky, kx, ci)) and f32 biases of conv1, layer1.conv1, layer1.conv2, layer1.downsample,
+    layer2.conv1, layer2.conv2, layer2.downsample."""
+    _req_cuda(patches, *ws, *bs)
+    n, ph, _, c = patches.shape
+    x = torch.empty(n, 16, 16, 32, device=patches.device, dtype=patches.dtype)
+    t1 = torch.empty(n, 8, 8, 32, device=patches.device, dtype=patches.dtype)
+    t2 = torch.empty(n, 4, 4, 32, device=patches.device, dtype=patches.dtype)
+    W = (ctypes.c_void_p * len(ws))(*[w.data_ptr() for w in ws])
+    B = (ctypes.c_void_p * len(bs))(*[b.data_ptr() for b in bs])
+    e0 = PROF.start()
+    L.check(L.load().comet_shallow_front_nhwc(dt(patches), _p(patches), W, B, _p(x), _p(t1), _p(t2), n, ph, c,
+                                              float(eps), stream()), "shallow_front")
+    if e0 is not None:
+        nb = sum(t.numel() * t.element_size() for t in (patches, x, t1, t2))
+        PROF.stop(e0, "comet_shallow_front", 2.0 * n * 32 * (256 * 72 + 64 * (288 + 288 + 32) + 16 * (288 + 288 + 32)),
+                  float(nb))
+    return x, t1, t2
+
+
+def shallow_front_ok(patches, ws, bs):
+    """comet_shallow_front_nhwc's conditions: everything the entry point rejects is rejected here."""
+    if patches.dim() != 4 or len(ws) != 7 or len(bs) != 7:
+        return False
+    n, ph, pw, c = patches.shape
+    ok = (patches.is_cuda and patches.dtype == torch.bfloat16 and patches.is_contiguous() and ph == 31 and pw == 31
+          and c == 8 and 0 < n < (1 << 31) // 256 and patches.data_ptr() % 16 == 0)
+    for w, b, k in zip(ws, bs, _SHALLOW_FRONT_K):
+        ok = ok and (w is not None and b is not None and w.is_cuda and b.is_cuda and w.dtype == torch.bfloat16
+                     and tuple(w.shape) == (32, k) and w.is_contiguous() and w.data_ptr() % 16 == 0
+                     and b.dtype == torch.float32 and tuple(b.shape) == (32,) and b.is_contiguous())
+    return bool(ok)
+
+
 def resize_pool_ok(x):
     """comet_resize_bilinear_pool_nhwc's conditions (c % 8, 16-B alignment, input image <= 32 KiB)."""
     n, h, w, c = x.shape

@@ -144,6 +144,38 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ---- InstanceNorm arithmetic of the one-wave-per-image kernel --------------------------------
+// Shared by in_wave_kernel (norm.hip) and the fused ShallowEncoder front (shallow_front.hip), which
+// must agree bit for bit. Contraction is off and the three fused multiply-adds are written out (they
+// are the ones hipcc formed in in_wave_kernel before the helpers existed), so every kernel that
+// inlines these rounds the same way whatever surrounds them.
+// one value into the moments shifted by K (the image's pixel 0 of this channel)
+__device__ __forceinline__ void in_moment_add(float v, float K, float& s1, float& s2) {
+#pragma clang fp contract(off)
+  const float d = v - K;
+  s1 += d;
+  s2 = __builtin_fmaf(d, d, s2);
+}
+// (a, b) = the shifted moments summed over the image, inv = 1 / pixels
+__device__ __forceinline__ void in_mean_rstd(float a, float b, float inv, float K, float eps, float& mu, float& rs) {
+#pragma clang fp contract(off)
+  const float m1 = a * inv;
+  float var = __builtin_fmaf(b, inv, -(m1 * m1));
+  var = var > 0.f ? var : 0.f;
+  mu = __builtin_fmaf(a, inv, K);
+  rs = rsqrtf(var + eps);
+}
+// relu?((v - mu) * rs) + r?, relu?
+__device__ __forceinline__ float in_normalize(float v, float mu, float rs, bool relu_inner, bool has_res, float r,
+                                              bool relu) {
+#pragma clang fp contract(off)
+  float o = (v - mu) * rs;
+  if (relu_inner) o = o > 0.f ? o : 0.f;
+  if (has_res) o += r;
+  if (relu) o = o > 0.f ? o : 0.f;
+  return o;
+}
+
 // block-wide sum for blockDim.x == 64*NW; scratch must hold NW floats
 template <int NW>
 __device__ __forceinline__ float block_sum(float v, float* scratch) {

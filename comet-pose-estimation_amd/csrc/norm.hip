@@ -596,7 +596,8 @@ in_apply_kernel(const T* __restrict__ x, const T* __restrict__ res, T* __restric
 // Small bf16 images (the fine ShallowEncoder: 65536 images of 16x16 / 8x8 / 4x4 x 32): one wave
 // per image holds the whole image in registers (NP 16-B vectors per lane), so the statistics need
 // no LDS / barrier (xor shuffles over the lanes of one channel group) and the apply pass no second
-// read; 4 images per workgroup. Same shifted-moment statistics as in_block_stats.
+// read; 4 images per workgroup. Same shifted-moment statistics as in_block_stats; the arithmetic is
+// common.hpp's in_moment_add / in_mean_rstd / in_normalize, shared with the fused ShallowEncoder front.
 template <int NP>
 __global__ void __launch_bounds__(256)
 in_wave_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ res, __bf16* __restrict__ y, int64_t n,
@@ -629,11 +630,7 @@ in_wave_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ res, __b
     float v[8];
     unpack(raw[k], v);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float d = v[e] - K[e];
-      s1[e] += d;
-      s2[e] += d * d;
-    }
+    for (int e = 0; e < 8; ++e) in_moment_add(v[e], K[e], s1[e], s2[e]);
   }
   const float inv = 1.f / (float)hw;
   float mu[8], rs[8];
@@ -644,11 +641,7 @@ in_wave_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ res, __b
       a += __shfl_xor(a, off, 64);
       b += __shfl_xor(b, off, 64);
     }
-    const float m1 = a * inv;
-    float var = b * inv - m1 * m1;
-    var = var > 0.f ? var : 0.f;
-    mu[e] = K[e] + m1;
-    rs[e] = rsqrtf(var + g.eps);
+    in_mean_rstd(a, b, inv, K[e], g.eps, mu[e], rs[e]);
   }
   const __bf16* rb = res ? res + img * g.hw * g.c : nullptr;
   __bf16* yb = y + img * g.hw * g.c;
@@ -660,13 +653,7 @@ in_wave_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ res, __b
     unpack(raw[k], v);
     if (rb) load8(rb + (int64_t)p * g.c + cg * 8, r);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float o = (v[e] - mu[e]) * rs[e];
-      if (g.relu_inner) o = o > 0.f ? o : 0.f;
-      if (rb) o += r[e];
-      if (g.relu) o = o > 0.f ? o : 0.f;
-      v[e] = o;
-    }
+    for (int e = 0; e < 8; ++e) v[e] = in_normalize(v[e], mu[e], rs[e], g.relu_inner, rb != nullptr, r[e], g.relu);
     store8(yb + (int64_t)p * g.c + cg * 8, v);
   }
 }

@@ -310,6 +310,18 @@ int comet_conv1x1_resize_pool_nhwc(const void* x, const void* up1, int64_t h1, i
                                    int64_t h2, int64_t w2, const void* weight, const float* bias, void* y,
                                    void* pool, void* pool2, int64_t n, int64_t c, int64_t h, int64_t w,
                                    int64_t oh, int64_t ow, void* stream);
+/* The fine ShallowEncoder's front (blocks.py:114-196 with modules.py:39-116): conv1 + InstanceNorm +
+ * ReLU and the two stride-2 ResidualBlocks in one kernel, bit for bit the seven comet_conv2d_nhwc
+ * (narrow kernel) and seven comet_instnorm_nhwc (one wave per image) calls it replaces, with no map
+ * but the three results in HBM. patches [n, 31, 31, 8] (RGB zero-padded to 8 channels), x
+ * [n, 16, 16, 32], tmp1 [n, 8, 8, 32], tmp2 [n, 4, 4, 32]: the tensors comet_conv1x1_resize_pool_nhwc
+ * reads. weights[7] / biases[7] (host arrays of device pointers) in the order conv1, layer1.conv1,
+ * layer1.conv2, layer1.downsample, layer2.conv1, layer2.conv2, layer2.downsample: dense bf16
+ * [32, kh * kw * cin] with columns (ky, kx, ci) (conv1's cin padded to 8) and f32 [32]. dtype must be
+ * COMET_BF16, p == 31, c == 8, n < 2^31 / 256, tensors and weights 16-B aligned. */
+int comet_shallow_front_nhwc(int dtype, const void* patches, const void* const* weights,
+                             const float* const* biases, void* x, void* tmp1, void* tmp2, int64_t n,
+                             int64_t p, int64_t c, float eps, void* stream);
 /* NHWC resize into a channel slice of a wider NHWC tensor (output pixel pitch ldy elements):
  * BasicEncoder's four up-sampled maps land directly in their torch.cat(dim=1) positions
  * (blocks.py:97-107), so the 416-channel concat is never copied. c, ldy % 8 == 0. */
