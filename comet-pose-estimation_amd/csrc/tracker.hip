@@ -618,8 +618,8 @@ __global__ void patch_gather_kernel(const float* __restrict__ images, const floa
     const int x0 = tlx < 0 ? 0 : (tlx > lim ? lim : tlx);
     const int y0 = tly < 0 ? 0 : (tly > lim ? lim : tly);
     const int64_t bs = t / N;
-    // the patch must lie inside the frame: the reference's H-for-both-axes clamp needs W >= H, and
-    // a NaN track coordinate has no defined floor
+    // the patch must lie inside the frame: the reference's H-for-both-axes clamp needs W >= H (the
+    // entry point rejects W < H), and a NaN track coordinate has no defined floor
     COMET_DASSERT(x0 >= 0 && x0 + P <= W && y0 >= 0 && y0 + P <= H && cx == cx && cy == cy);
     const int64_t pix = (int64_t)(y0 + py) * W + (x0 + px), plane = (int64_t)H * W;
     const float* src = images + bs * 3 * plane + pix;
@@ -1006,6 +1006,9 @@ extern "C" int comet_patch_gather(int dtype_out, const float* images, const floa
                                   int pradius, int cpad, void* stream) {
   COMET_CHECK_ARG(images && coarse && patches && topleft && query, "comet_patch_gather: null pointer");
   COMET_CHECK_ARG(H >= 2 * pradius + 1 && W >= 2 * pradius + 1, "comet_patch_gather: image smaller than a patch");
+  // the kernel clamps both patch origins with H - P as the reference does: with W < H the clamped x
+  // origin can pass W - P and the patch would be read past the row or the frame
+  COMET_CHECK_ARG(W >= H, "comet_patch_gather: W >= H required (both patch origins are clamped with H, as in the reference)");
   COMET_CHECK_ARG(cpad >= 3 && cpad <= 8, "comet_patch_gather: cpad must be in [3, 8]");
   COMET_CHECK_ARG(cpad != 8 || (uintptr_t)patches % 32 == 0, "comet_patch_gather: cpad 8 needs a 32-B aligned output");
   const int P = 2 * pradius + 1;

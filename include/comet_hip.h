@@ -415,7 +415,10 @@ int comet_coords_update(int dtype_delta, float* coords, const void* delta, int64
 int comet_avgpool2_nhwc(int dtype, const void* x, void* y, int64_t n, int H, int W, int C, void* stream);
 /* refine_track.py:74-131: patches NHWC [B*N*S, P, P, cpad] in (b, n, s) order (RGB in channels
  * 0..2, channels 3..cpad-1 zero: cpad 8 lets the first conv run as an implicit GEMM), topleft
- * [B,S,N,2] (int, unclamped), query [B*N,2] = frac(coarse[:, 0]) + pradius */
+ * [B,S,N,2] (int, unclamped), query [B*N,2] = frac(coarse[:, 0]) + pradius. Both patch origins
+ * are clamped to [0, H - P] (the reference uses H for x as well), so the entry point requires
+ * H >= P and W >= H and returns COMET_EINVAL otherwise (W < H would read past the row); track
+ * coordinates must not be NaN. */
 int comet_patch_gather(int dtype_out, const float* images, const float* coarse, void* patches,
                        int* topleft, float* query, int64_t B, int S, int64_t N, int H, int W,
                        int pradius, int cpad, void* stream);

@@ -2,9 +2,11 @@
 check hooks (comet_amd/debug.py).
 
 * In a fresh process with COMET_DEBUG=1 (libcomet_hip_debug.so): a patch gather inside the frame
-  passes; one whose patch leaves a W < H frame (the reference clamps both axes with H,
-  refine_track.py) fails its COMET_DASSERT and the op raises CometHipError naming it -- the
-  reads stay inside the allocation (the frames are a slice of a larger buffer).
+  passes and records nothing; a W < H frame never reaches the kernel (the entry point rejects it:
+  the reference clamps both patch origins with H, refine_track.py); a ring gather whose device slot
+  list names a slot outside the ring -- unlike the host copy the library checks before it launches
+  -- fails its COMET_DASSERT and the op raises CometHipError naming it. The kernel skips such a
+  slot, so nothing is read or written outside the ring.
 * FiniteCheck names the first submodule whose output holds a NaN; check_grads the first
   parameter whose gradient does."""
 import os
@@ -25,20 +27,35 @@ import torch
 from comet_amd import _lib as L, debug, ops
 assert L.LIB_PATH.endswith("libcomet_hip_debug.so"), L.LIB_PATH
 assert debug.debug_library() and debug.debug_flags() == 0
-big = torch.rand(2, 2, 3, 40, 32, device="cuda")   # H = 40 > W = 32
-imgs = big[:1]                                       # B = 1, S = 2; reads past it stay in `big`
-coarse = torch.full((1, 2, 4, 2), 16.0, device="cuda")
-ops.patch_gather(imgs, coarse, 15, torch.float32)  # x0 = 1, 1 + 31 <= 32: inside
+imgs = torch.rand(1, 2, 3, 32, 40, device="cuda")   # H = 32 <= W = 40
+coarse = torch.full((1, 2, 4, 2), 30.0, device="cuda")
+ops.patch_gather(imgs, coarse, 15, torch.float32)  # x0 = min(15, H - 31 = 1) = 1: inside
 torch.cuda.synchronize()
-coarse[..., 0] = 30.0                                # x0 = min(15, H - 31 = 9) = 9: 9 + 31 > W
+assert debug.debug_flags() == 0
 try:
-    ops.patch_gather(imgs, coarse, 15, torch.float32)
+    ops.patch_gather(imgs.transpose(3, 4).contiguous(), coarse, 15, torch.float32)  # H = 40 > W = 32
+except L.CometHipError as e:
+    assert "W >= H" in str(e), str(e)
+    assert debug.debug_flags() == 0                  # rejected on the host: nothing ran
+else:
+    raise SystemExit("the W < H frame was not rejected")
+import ctypes
+ring = torch.arange(8 * 64, dtype=torch.float32, device="cuda").reshape(8, 64)
+win = torch.zeros(4, 64, device="cuda")
+host = (ctypes.c_int32 * 4)(5, 6, 7, 0)
+slots = torch.tensor([5, 6, 7, 0], dtype=torch.int32, device="cuda")
+ops.ring_gather([(ring, win)], slots, host)
+torch.cuda.synchronize()
+assert torch.equal(win, ring[[5, 6, 7, 0]]) and debug.debug_flags() == 0
+slots[2] = 11                                        # outside the ring of 8; the host copy still says 7
+try:
+    ops.ring_gather([(ring, win)], slots, host)
 except L.CometHipError as e:
     assert "index check failed" in str(e), str(e)
     assert debug.debug_flags() != 0
     print("DEBUG-OK", e)
 else:
-    raise SystemExit("the out-of-frame patch was not reported")
+    raise SystemExit("the slot outside the ring was not reported")
 """
 
 
