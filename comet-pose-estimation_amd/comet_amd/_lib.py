@@ -191,6 +191,8 @@ SIGNATURES = {
                                _INT, _INT, _INT, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "comet_track_carry": (_INT, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _INT, _INT, _INT, _INT, _INT,
                                  _INT, _INT, _INT, _INT, _F, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "comet_track_warm": (_INT, [c_vp, c_vp, c_vp, c_vp, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _F, _F, c_vp, c_vp,
+                                c_vp]),
 }
 
 _lib = None

@@ -636,14 +636,30 @@ def _stream_carry(cfg, sp, sift, candidate_fn, device):
     carry_border (0) / carry_min_score (required) / detect_every (1) -> the carry keywords of PoseStream
     / StreamPool ({} with carry off). candidate_fn: default keypoint_candidates of the detectors."""
     if not _get(cfg, "stream.carry", False):
+        if _get(cfg, "stream.warm", False):
+            raise ValueError("cfg.stream.warm needs cfg.stream.carry: the warm start follows the carried tracks")
         return {}
     from .stream import keypoint_candidates
     if candidate_fn is None:
         candidate_fn = keypoint_candidates(sp if sp is not None else _keypoint_init(cfg, device), sift)
-    return dict(carry=True, carry_tracks=int(_get(cfg, "stream.carry_tracks", _get(cfg, "train.track_num", 512))),
-                carry_cell=int(_get(cfg, "stream.carry_cell", 8)), carry_border=int(_get(cfg, "stream.carry_border", 0)),
-                carry_min_score=_get(cfg, "stream.carry_min_score", None),
-                detect_every=int(_get(cfg, "stream.detect_every", 1)), candidate_fn=candidate_fn)
+    kw = dict(carry=True, carry_tracks=int(_get(cfg, "stream.carry_tracks", _get(cfg, "train.track_num", 512))),
+              carry_cell=int(_get(cfg, "stream.carry_cell", 8)), carry_border=int(_get(cfg, "stream.carry_border", 0)),
+              carry_min_score=_get(cfg, "stream.carry_min_score", None),
+              detect_every=int(_get(cfg, "stream.detect_every", 1)), candidate_fn=candidate_fn)
+    if _get(cfg, "stream.warm", False):
+        kw.update(warm=True, warm_mode=_get(cfg, "stream.warm_mode", "hold"), warm_iters=_get(cfg, "stream.warm_iters", None))
+    return kw
+
+
+# cfg.stream.warm: this column after the carry columns, per hop
+WARM_FIELDS = ("warm",)
+
+
+def _carry_fields(carry):
+    """The trailing CSV columns of the keywords _stream_carry returned."""
+    if not carry:
+        return ()
+    return CARRY_FIELDS + (WARM_FIELDS if carry.get("warm") else ())
 
 
 def _carry_counts(r):
@@ -674,6 +690,8 @@ def _log_hop(logger, fields, r, window, ms, last=None):
         row = dict(zip(STREAM_FIELDS, [r.frame_index, r.frame_index + window - 1] + enc + [ms]))
         if r.track_src is not None:
             row.update(zip(CARRY_FIELDS, _carry_counts(r)))
+        if r.track_warm is not None:  # slots whose coarse tracker started warm (carried, or a pad of a carried slot)
+            row[WARM_FIELDS[0]] = int((r.track_warm > 0).sum())
         positions = range(r.final) if r.final is not None else None
     else:
         row, positions = last, range(r.final, window)
@@ -703,7 +721,10 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
     cfg.stream.carry (default false; with carry_cell, carry_border, carry_tracks, detect_every and the
     required carry_min_score) turns track carry on (PoseStream carry=True): the queries come from the
     carried tracks and candidate_fn (default: keypoint_candidates of the detectors), query_points must
-    be None, and the CSV gains the trailing columns survivors, born, padded. Off: the CSV is what it was."""
+    be None, and the CSV gains the trailing columns survivors, born, padded. Off: the CSV is what it was.
+    cfg.stream.warm (default false; needs cfg.stream.carry; with warm_mode "hold" / "velocity" and warm_iters,
+    default cfg.track_trainit) starts the coarse tracker of every hop but the first from the previous
+    window's tracks (PoseStream warm=True); the CSV gains a last column warm, the slots that started so."""
     from .data import crop_resize_normalize
     from .stream import PoseStream, keypoint_query
     if not _get(cfg, "stream.enable", False):
@@ -723,7 +744,7 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
                         precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight,
                         **carry)
     if carry:
-        fields = tuple(fields) + CARRY_FIELDS
+        fields = tuple(fields) + _carry_fields(carry)
     logger = CsvLogger(csv_path, fields)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     hops, last = 0, None
@@ -754,7 +775,8 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
     cfg.stream.fuse / fuse_weight as stream_eval: the fused columns, and a flush of its last window
     when a sequence ends (all hops of a push are fused by one launch; every anchor must then carry
     one ratio and one dataset). cfg.stream.carry and candidate_fn: as stream_eval (StreamPool
-    carry=True; a sequence that takes over a stream starts with fresh ids)."""
+    carry=True; a sequence that takes over a stream starts with fresh ids). cfg.stream.warm, warm_mode and
+    warm_iters: as stream_eval (StreamPool warm=True)."""
     from .data import crop_resize_normalize
     from .stream import StreamPool, keypoint_query
     if not _get(cfg, "stream.enable", False):
@@ -780,7 +802,7 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
                       precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight,
                       **carry)
     if carry:
-        fields = tuple(fields) + CARRY_FIELDS
+        fields = tuple(fields) + _carry_fields(carry)
     lasts = {}  # stream id -> (last result, its row): flushed when the sequence ends
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     seqs = iter(sequences)

@@ -39,14 +39,16 @@ class COMET(nn.Module):
                 p.requires_grad = False
 
     def forward(self, image, gt_cameras=None, training=True, tracks=None, tracks_visibility=None, crop_params=None,
-                epoch=-1, frame_cache=None):
+                epoch=-1, frame_cache=None, track_init=None, track_iters=None):
         if training:
             return self.forward_all(image, gt_cameras=gt_cameras, training=training, tracks=tracks,
-                                    tracks_visibility=tracks_visibility, frame_cache=frame_cache)
+                                    tracks_visibility=tracks_visibility, frame_cache=frame_cache,
+                                    track_init=track_init, track_iters=track_iters)
         assert image.shape[0] == 1, f"evaluation processes one sequence at a time, got batch {image.shape[0]}"
         with torch.no_grad():
             return self.forward_all(image, gt_cameras=gt_cameras, training=training, tracks=tracks,
-                                    tracks_visibility=tracks_visibility, frame_cache=frame_cache)
+                                    tracks_visibility=tracks_visibility, frame_cache=frame_cache,
+                                    track_init=track_init, track_iters=track_iters)
 
     @torch.no_grad()
     def frame_stages(self, frames):
@@ -63,10 +65,13 @@ class COMET(nn.Module):
         return FrameCache(fmaps=fmaps, refine_frames=refine_frames, tokens=tokens)
 
     def forward_all(self, image, preliminary_cameras=None, gt_cameras=None, training=True, tracks=None,
-                    tracks_visibility=None, frame_cache=None):
+                    tracks_visibility=None, frame_cache=None, track_init=None, track_iters=None):
         """E2Epose2.py:151-266 (fine_tracker=True, softmax_refine=False, track_conf=False).
         frame_cache (FrameCache, optional): the per-frame stages' outputs for these B x T frames,
-        computed earlier; `image` then only supplies the shape."""
+        computed earlier; `image` then only supplies the shape.
+        track_init (optional): the coarse predictor's coords_init, f32 [B, N, T, 2] in its grid units,
+        updated in place; track_iters (optional): the coarse iterations of this call instead of
+        cfg.track_trainit (DESIGN.md "Warm start"). Both None: the call runs as it always has."""
         B, T, C, H, W = image.shape
         cfg = self.cfg
         predictions = {}
@@ -79,8 +84,10 @@ class COMET(nn.Module):
                 else:
                     fmaps = frame_cache.fmaps
                 coarse_lists, vis_e, _, _, _ = tp.coarse_predictor(query_points=tracks[:, 0], fmaps=fmaps,
-                                                                   iters=cfg["track_trainit"],
-                                                                   down_ratio=tp.coarse_down_ratio, return_feat=True)
+                                                                   iters=cfg["track_trainit"] if track_iters is None
+                                                                   else int(track_iters),
+                                                                   down_ratio=tp.coarse_down_ratio, return_feat=True,
+                                                                   coords_init=track_init)
                 coarse = coarse_lists[-1]
                 if cfg["fine_tracker"]:
                     refined, score, inverted_score = refine_track(

@@ -61,8 +61,14 @@ class BaseTrackerPredictor(nn.Module):
 
     @torch.no_grad()
     def forward(self, query_points, fmaps=None, iters=4, return_feat=False, down_ratio=1, is_train=False,
-                track_feats=None, TRACKorPOSE=False, ind=0, pyramid1=None, pyramid2=None):
+                track_feats=None, TRACKorPOSE=False, ind=0, pyramid1=None, pyramid2=None, coords_init=None):
         """query_points [B, N, 2]; fmaps NHWC [B, S, HH, WW, C] (compute dtype).
+        coords_init (optional): f32 [B, N, S, 2], where the iterations start, in the units they run in
+        (query_points / down_ratio / stride when down_ratio > 1), instead of the query point in every
+        frame (comet_track_warm, DESIGN.md "Warm start"). Contiguous and owned by this call: it is
+        updated in place. Its frame 0 must equal the scaled query points (not checked); the query
+        features, the position embedding and the initial track features are taken at the query points
+        either way.
         Returns (coord_preds list of [B, S, N, 2], vis [B, S, N] or None, track_feats [B, N, S, C],
         query_track_feat [B, N, C], conf None)."""
         B, N, _ = query_points.shape
@@ -72,7 +78,14 @@ class BaseTrackerPredictor(nn.Module):
         if down_ratio > 1:
             q = q / float(down_ratio)
             q = q / float(self.stride)
-        coords = q.reshape(B, N, 1, 2).repeat(1, 1, S, 1).contiguous()  # [B, N, S, 2]
+        if coords_init is None:
+            coords = q.reshape(B, N, 1, 2).repeat(1, 1, S, 1).contiguous()  # [B, N, S, 2]
+        else:
+            if (coords_init.shape != (B, N, S, 2) or coords_init.dtype != torch.float32 or coords_init.device != dev
+                    or not coords_init.is_contiguous()):
+                raise ValueError(f"coords_init must be a dense f32 [{B}, {N}, {S}, 2] tensor on {dev}, got "
+                                 f"{tuple(coords_init.shape)} {coords_init.dtype} on {coords_init.device}")
+            coords = coords_init
         fm0 = fmaps[:, 0]
         query_feat = ops.sample_bilinear(fm0, q, border=True)  # [B, N, C]
         track_feats = query_feat.reshape(B, N, 1, C).repeat(1, 1, S, 1).contiguous()  # f32 [B, N, S, C]

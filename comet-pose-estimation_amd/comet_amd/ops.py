@@ -746,6 +746,44 @@ def track_carry(tracks, score, ids, age, next_id, prev_valid, s, H, W, cell, bor
     return out
 
 
+class WarmOut(NamedTuple):
+    coords: torch.Tensor  # [n, N, T, 2] f32 starting coordinates in the coarse predictor's grid units
+    warm: torch.Tensor    # [n, N] int32: 0 cold, 1 carried, 2 pad copy of a carried slot, -1 fallen back
+
+
+WARM_MODES = {"hold": 0, "velocity": 1}
+
+
+def track_warm(prev, src, query, prev_valid, s, H, W, mode, div0, div1):
+    """comet_track_warm (include/comet_hip.h): the coarse tracker's starting coordinates of n new
+    windows from the previous windows' pred_tracks prev [n, T, N, 2] f32 and the src [n, N] int32 /
+    query [n, N, 2] f32 outputs of ops.track_carry on the same prev / prev_valid [n] int32, in one
+    launch. mode: 0 / "hold" or 1 / "velocity"; div0, div1: the predictor's divisions (1, 1 for none)
+    -> WarmOut (new tensors)."""
+    _req_cuda(prev, src, query, prev_valid)
+    if prev.dim() != 4 or prev.shape[3] != 2 or prev.dtype != torch.float32 or not prev.is_contiguous():
+        raise L.CometHipError(f"track_warm: prev must be a dense f32 [n, T, N, 2] tensor, got {tuple(prev.shape)} "
+                              f"{prev.dtype}")
+    n, T, N = prev.shape[:3]
+    if query.shape != (n, N, 2) or query.dtype != torch.float32 or not query.is_contiguous():
+        raise L.CometHipError("track_warm: query must be a dense f32 [n, N, 2] tensor")
+    for name, t, shape in (("src", src, (n, N)), ("prev_valid", prev_valid, (n,))):
+        if t.shape != shape or t.dtype != torch.int32 or not t.is_contiguous():
+            raise L.CometHipError(f"track_warm: {name} must be a dense int32 {list(shape)} tensor")
+    dev = prev.device
+    if any(t.device != dev for t in (src, query, prev_valid)):
+        raise L.CometHipError("track_warm: every tensor must be on one device")
+    mode = WARM_MODES.get(mode, mode)
+    out = WarmOut(torch.empty(n, N, T, 2, device=dev), torch.empty(n, N, device=dev, dtype=torch.int32))
+    e0 = PROF.start()
+    L.check(L.load().comet_track_warm(_p(prev), _p(src), _p(query), _p(prev_valid), n, T, N, int(s), int(H), int(W),
+                                      int(mode), float(div0), float(div1), _p(out.coords), _p(out.warm), stream()),
+            "track_warm")
+    if e0 is not None:
+        PROF.stop(e0, "comet_track_warm", 0.0, float(n * N * (T * 16 + 16)))
+    return out
+
+
 def resize_bilinear_pool(x, oh, ow):
     """NHWC x [n, h, w, c] -> (y [n, oh, ow, c] bilinear, align_corners=True; its 2 x 2 average
     pool [n, oh // 2, ow // 2, c]) in one kernel: resize_bilinear + avgpool2_nhwc bit for bit."""

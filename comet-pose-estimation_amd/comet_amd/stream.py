@@ -18,7 +18,8 @@ them once per frame, keeps their outputs in device rings, and for every hop gath
                  per push); usable on its own with any [n, T, 7] encodings
   CarrySchedule  which hop is a stream's first and on which hops the detector runs, host only
   TrackCarry     persistent track ids: the next window's queries are this window's tracks on the frame
-                 that becomes first (comet_track_carry, one launch per push)
+                 that becomes first (comet_track_carry, one launch per push); with warm_mode also where
+                 the coarse tracker starts in the new window (comet_track_warm, one launch per push)
   keypoint_query query_fn from the SuperPoint / SIFT detectors of comet_amd.keypoints
   keypoint_candidates  candidate_fn of the same detectors for carry=True: raw detections, no padding
 """
@@ -99,21 +100,23 @@ class _StreamFields(NamedTuple):
 
 
 class StreamResult(_StreamFields):
-    """The tuple above, followed by three fields that are attributes only (the tuple keeps its twelve
+    """The tuple above, followed by four fields that are attributes only (the tuple keeps its twelve
     positions, so code that unpacks or slices a result sees what it saw): with carry=True the identity
-    of the track in every query slot (TrackCarry), else None."""
+    of the track in every query slot (TrackCarry), else None; with warm=True also how the coarse
+    tracker started in every slot, else None."""
     track_ids: Optional[torch.Tensor] = None  # [N] int32, -1: a pad
     track_age: Optional[torch.Tensor] = None  # [N] int32 hops the track has lived
     track_src: Optional[torch.Tensor] = None  # [N] int32: j carried, -1 - c born from candidate c, else a pad
+    track_warm: Optional[torch.Tensor] = None  # [N] int32: 0 cold, 1 carried, 2 pad of a carried slot, -1 fallen back
 
     def _replace(self, **kw):
         r = super()._replace(**kw)
         r.__dict__.update(self.__dict__)
         return r
 
-    def with_tracks(self, track_ids, track_age, track_src):
+    def with_tracks(self, track_ids, track_age, track_src, track_warm=None):
         r = self._replace()
-        r.track_ids, r.track_age, r.track_src = track_ids, track_age, track_src
+        r.track_ids, r.track_age, r.track_src, r.track_warm = track_ids, track_age, track_src, track_warm
         return r
 
 
@@ -366,12 +369,23 @@ class TrackCarry:
     for all the hops given (at most one per stream): a track that is still alive on the frame that
     is now first (inside the frame and the mask, score >= min_score) and holds its grid cell keeps
     its slot and id, free slots take candidates in detector order, the rest is padded (id -1). On a
-    hop where the detector does not run pass no candidates (CarrySchedule.detects)."""
+    hop where the detector does not run pass no candidates (CarrySchedule.detects).
+
+    warm_mode "hold" or "velocity" (default None: off): step() also launches comet_track_warm, right
+    after comet_track_carry and on the same previous tracks, and leaves its outputs in `warm`
+    (ops.WarmOut: the coarse tracker's starting coordinates [n, N, T, 2] in the units warm_div =
+    (down_ratio, stride) gives, and per slot how it starts; DESIGN.md "Warm start"). The CarryOut is
+    what it is without."""
 
     _TABLES_MAX = 1024
 
-    def __init__(self, window, stride=1, streams=1, tracks=512, cell=8, border=0, min_score=None, detect_every=1):
+    def __init__(self, window, stride=1, streams=1, tracks=512, cell=8, border=0, min_score=None, detect_every=1,
+                 warm_mode=None, warm_div=(1.0, 1.0)):
         self.sched = CarrySchedule(window, stride, streams, detect_every)
+        if warm_mode is not None and warm_mode not in ops.WARM_MODES:
+            raise ValueError(f'warm_mode must be "hold" or "velocity", got {warm_mode!r}')
+        self.warm_mode, self.warm_div = warm_mode, (float(warm_div[0]), float(warm_div[1]))
+        self.warm = None  # ops.WarmOut of the last step (warm_mode given)
         if min_score is None:
             raise ValueError("track carry needs carry_min_score: the lowest pred_score a carried track may have "
                              "(there is no default; DESIGN.md \"Track carry\" records the value the benchmark used)")
@@ -480,6 +494,9 @@ class TrackCarry:
             ids, age, next_id = self.ids.index_select(0, idx), self.age.index_select(0, idx), self.next_id.index_select(0, idx)
         out = ops.track_carry(tr, sc, ids, age, next_id, prev_valid, self.sched.stride, H, W, self.cell, self.border,
                               self.min_score, cand, cand_n, mask)
+        if self.warm_mode is not None:
+            self.warm = ops.track_warm(tr, out.src, out.query, prev_valid, self.sched.stride, H, W, self.warm_mode,
+                                       *self.warm_div)
         if whole:
             self.ids, self.age = out.ids, out.age  # (new tensors: results handed out earlier stay as they were)
         else:
@@ -508,8 +525,26 @@ def _check_carry(carry, candidate_fn, query_points=None):
         raise ValueError("explicit query_points together with carry=True: the carried tracks are the query points")
 
 
-def _carry_fields(co, b):
-    return co.ids[b], co.age[b], co.src[b]
+def _carry_fields(co, b, wo=None):
+    return co.ids[b], co.age[b], co.src[b], None if wo is None else wo.warm[b]
+
+
+def _check_warm(warm, carry, warm_mode, warm_iters):
+    if warm_mode not in ops.WARM_MODES:
+        raise ValueError(f'warm_mode must be "hold" or "velocity", got {warm_mode!r}')
+    if warm_iters is not None and int(warm_iters) < 1:
+        raise ValueError(f"warm_iters must be at least 1, got {warm_iters}")
+    if warm and not carry:
+        raise ValueError("warm=True needs carry=True: the warm start follows the carried tracks")
+
+
+def _warm_div(model):
+    """The two divisions of the model's coarse predictor, (down_ratio, stride), or (1, 1) where it
+    divides by nothing (BaseTrackerPredictor.forward)."""
+    tp = model.track_predictor
+    if tp.coarse_down_ratio > 1:
+        return float(tp.coarse_down_ratio), float(tp.coarse_predictor.stride)
+    return 1.0, 1.0
 
 
 class PoseStream:
@@ -561,21 +596,35 @@ class PoseStream:
     detector keypoints on frame 0, and what carried queries do to pose accuracy is unmeasured beyond
     DESIGN.md "Track carry" (whose benchmark used 0.0). With carry=False nothing changes.
 
+    warm=True (needs carry=True) also starts the coarse tracker of every hop but the stream's first where
+    the tracks already are (comet_track_warm, DESIGN.md "Warm start"): a carried slot starts on the previous
+    window's refined track shifted by the stride; the `stride` frames the previous window has not seen
+    repeat its last position (warm_mode="hold") or continue its last step, clamped to the frame
+    ("velocity"); born slots, pads of born slots and slots whose previous track is not finite start on
+    their query point as always. warm_iters (None: cfg.track_trainit) is the number of coarse iterations
+    of those hops; the first hop after construction or reset is cold and runs cfg.track_trainit. Results
+    then carry track_warm. What a warm start and fewer iterations do to pose accuracy on real sequences is
+    unmeasured, so the option is off by default. With warm=False nothing changes.
+
     One stream (batch 1). The model is used as is (its eval / train mode included)."""
 
     def __init__(self, model, window, stride=1, capacity=None, query_fn=None, anchor=None, precision=None,
                  fuse=False, fuse_weight=None, carry=False, carry_tracks=512, carry_cell=8, carry_border=0,
-                 carry_min_score=None, detect_every=1, candidate_fn=None, mask_fn=None):
+                 carry_min_score=None, detect_every=1, candidate_fn=None, mask_fn=None, warm=False, warm_mode="hold",
+                 warm_iters=None):
         self.model = model
         self.sched = RingSchedule(window, stride, capacity)
         self.query_fn = query_fn
         self.carry, self.candidate_fn, self.mask_fn = bool(carry), candidate_fn, mask_fn
+        _check_warm(warm, self.carry, warm_mode, warm_iters)
+        self.warm, self.warm_mode = bool(warm), warm_mode
+        self.warm_iters = None if warm_iters is None else int(warm_iters)
         self._carry = None
         if self.carry:
             self.sched.chain_index()  # raises unless stride < window
             _check_carry(True, candidate_fn)
             self._carry = TrackCarry(window, stride, 1, carry_tracks, carry_cell, carry_border, carry_min_score,
-                                     detect_every)
+                                     detect_every, warm_mode if self.warm else None)
         self.precision = precision if precision is not None else _model_precision(model)
         _check_fuse(fuse, fuse_weight, anchor is not None)
         self.fuse, self.fuse_weight = bool(fuse), fuse_weight
@@ -644,19 +693,27 @@ class PoseStream:
     def _hop(self, hop, query_points):
         T = self.sched.window
         cache = self._gather(hop.head)
-        co = None
+        co = wo = None
+        extra = {}
         if self.carry:
             frame = cache.refine_frames[0, 0]
             cand = self.candidate_fn(frame) if self._carry.detects(0) else None
             mask = self.mask_fn(frame) if self.mask_fn is not None else None
+            first = self._carry.sched.is_first(0)
+            if self.warm:
+                self._carry.warm_div = _warm_div(self.model)
             co = self._carry.step([0], frame.shape[-2], frame.shape[-1], [cand], [mask])
             query_points = co.query[0]
+            if self.warm:
+                wo = self._carry.warm
+                if not first:  # (a first hop is cold and runs the config's iterations: the call as it always was)
+                    extra = dict(track_init=wo.coords, track_iters=self.warm_iters)
         elif query_points is None:
             query_points = self.query_fn(cache.refine_frames[0, 0])
         q = query_points.to(self._tables.device, torch.float32)
         tracks = q[None, None].expand(1, T, -1, 2)
         # (with a frame_cache the model reads only the shape of its image argument)
-        out = self.model(cache.refine_frames, training=False, tracks=tracks, frame_cache=cache)
+        out = self.model(cache.refine_frames, training=False, tracks=tracks, frame_cache=cache, **extra)
         enc = out["pred_pose_enc"]
         tr = out.get("pred_tracks")
         sc = out.get("_track_predictions", {}).get("pred_score")
@@ -664,7 +721,7 @@ class PoseStream:
         res = StreamResult(hop.frame_index, enc, None if tr is None else tr[0], None if sc is None else sc[0])
         if co is not None:
             self._carry.update([0], tr, sc)
-            res = res.with_tracks(*_carry_fields(co, 0))
+            res = res.with_tracks(*_carry_fields(co, 0, wo))
         if self.fuse:
             w = _score_weights(sc) if self.fuse_weight == "score" else None
             return res._replace(**_fused_fields(self._fuser.fuse(enc, [(0, hop)], w), 0, self._fuser.sched.final))
@@ -814,6 +871,10 @@ class StreamPool:
     set of intrinsics). carry / carry_* / detect_every / candidate_fn / mask_fn: as PoseStream's; every
     carried hop has carry_tracks queries, so the hops due in a push are one group, and one
     comet_track_carry launch serves them all; reset(stream) restarts that stream's ids and ages.
+    warm / warm_mode / warm_iters: as PoseStream's; one comet_track_warm launch serves all the hops
+    due. A stream's first hop runs cfg.track_trainit coarse iterations and a later one warm_iters, so
+    when both fall in one push and the two counts differ they run as two batched calls (first hops,
+    then later hops); otherwise the hops due stay one group. The result order is unchanged.
 
     push() -> [(stream id, StreamResult)] ordered by stream id. The tensors of a result are views
     of the batched outputs. The model is used as is (its eval / train mode included)."""
@@ -822,17 +883,21 @@ class StreamPool:
 
     def __init__(self, model, streams, window, stride=1, capacity=None, query_fn=None, anchors=None, precision=None,
                  fuse=False, fuse_weight=None, carry=False, carry_tracks=512, carry_cell=8, carry_border=0,
-                 carry_min_score=None, detect_every=1, candidate_fn=None, mask_fn=None):
+                 carry_min_score=None, detect_every=1, candidate_fn=None, mask_fn=None, warm=False, warm_mode="hold",
+                 warm_iters=None):
         self.model = model
         self.sched = PoolSchedule(streams, window, stride, capacity)
         self.query_fn = query_fn
         self.carry, self.candidate_fn, self.mask_fn = bool(carry), candidate_fn, mask_fn
+        _check_warm(warm, self.carry, warm_mode, warm_iters)
+        self.warm, self.warm_mode = bool(warm), warm_mode
+        self.warm_iters = None if warm_iters is None else int(warm_iters)
         self._carry = None
         if self.carry:
             self.sched.scheds[0].chain_index()  # raises unless stride < window
             _check_carry(True, candidate_fn)
             self._carry = TrackCarry(window, stride, streams, carry_tracks, carry_cell, carry_border, carry_min_score,
-                                     detect_every)
+                                     detect_every, warm_mode if self.warm else None)
         self.precision = precision if precision is not None else _model_precision(model)
         _check_fuse(fuse, fuse_weight, anchors is not None)
         self.fuse, self.fuse_weight = bool(fuse), fuse_weight
@@ -939,24 +1004,50 @@ class StreamPool:
         firsts = [self._rings[1][self.sched.slot(sid, hop.frame_index)] for sid, hop in hops]
         cands = [self.candidate_fn(f) if self._carry.detects(sid) else None for f, (sid, _) in zip(firsts, hops)]
         masks = [self.mask_fn(f) if self.mask_fn is not None else None for f in firsts]
+        if self.warm:
+            self._carry.warm_div = _warm_div(self.model)
         return self._carry.step([sid for sid, _ in hops], self._hw[0], self._hw[1], cands, masks)
 
-    def _hops(self, hops, qs, pos, fused=None, co=None):
+    def _warm_groups(self, firsts):
+        """carry=True: the hops due (firsts[i]: hop i is its stream's first) -> [(positions, warm start
+        given, coarse iterations or None for the config's)], one batched call each. One group unless
+        warm=True and first and later hops fall together whose iteration counts differ."""
+        every = list(range(len(firsts)))
+        if not self.warm or all(firsts):
+            return [(every, False, None)]
+        iters = self.warm_iters
+        if iters is None or iters == int(self.model.cfg["track_trainit"]) or not any(firsts):
+            return [(every, True, None if any(firsts) else iters)]
+        return [([i for i in every if firsts[i]], False, None), ([i for i in every if not firsts[i]], True, iters)]
+
+    def _hops(self, hops, qs, pos, fused=None, co=None, wo=None, warm=False, iters=None):
         """The hops hops[i], i in pos (all with N query points) as one batched call ->
         [(stream, StreamResult)] in the order of pos. fused (fuse=True): a list that takes the
         group's (pred_pose_enc, pred_score); the absolute poses are then left to _fuse. co
-        (carry=True): the ops.CarryOut whose rows are the hops' queries (pos is then every hop)."""
+        (carry=True): the ops.CarryOut whose rows are the queries of all the hops due; wo (warm=True):
+        the ops.WarmOut of the same hops, whose coordinates start the coarse tracker when `warm`;
+        iters: the coarse iterations of this call (None: the config's)."""
         from .models.E2Epose2 import FrameCache
         T, n = self.sched.window, len(pos)
+        rows = None if co is None or n == len(hops) else self._table(pos)[0].long()
         table, table_host = self._table(self.sched.table([hops[i] for i in pos]))
         wins = [None if w is None else w[:n * T] for w in self._wins]
         ops.ring_gather([(r, w) for r, w in zip(self._rings, wins) if r is not None], table, table_host)
         fm, fr, tok = wins
         cache = FrameCache(fmaps=None if fm is None else fm.view(n, T, *fm.shape[1:]),
                            refine_frames=fr.view(n, T, *fr.shape[1:]), tokens=tok)
-        tracks = (co.query if co is not None else torch.stack([qs[i] for i in pos]))[:, None].expand(n, T, -1, 2)
+        if co is not None:
+            q = co.query if rows is None else co.query.index_select(0, rows)
+        else:
+            q = torch.stack([qs[i] for i in pos])
+        tracks = q[:, None].expand(n, T, -1, 2)
+        extra = {}
+        if warm:  # (the predictor updates its starting coordinates in place: wo.coords, or the copy, is this call's)
+            extra["track_init"] = wo.coords if rows is None else wo.coords.index_select(0, rows)
+        if iters is not None:
+            extra["track_iters"] = iters
         # (with a frame_cache the model reads only the shape of its image argument)
-        out = self.model.forward_all(cache.refine_frames, training=False, tracks=tracks, frame_cache=cache)
+        out = self.model.forward_all(cache.refine_frames, training=False, tracks=tracks, frame_cache=cache, **extra)
         enc = out["pred_pose_enc"]  # [n * T, 7]
         tr = out.get("pred_tracks")
         sc = out.get("_track_predictions", {}).get("pred_score")
@@ -974,7 +1065,7 @@ class StreamPool:
             results.append((sid, StreamResult(hop.frame_index, e, None if tr is None else tr[b],
                                               None if sc is None else sc[b], R, Tx)))
             if co is not None:
-                results[-1] = (sid, results[-1][1].with_tracks(*_carry_fields(co, b)))
+                results[-1] = (sid, results[-1][1].with_tracks(*_carry_fields(co, i, wo)))
         return results
 
     def _fuse(self, hops, results, fused):
@@ -1021,9 +1112,13 @@ class StreamPool:
                              slot_table, slot_host)
             if hops:
                 fused, order = ([] if self.fuse else None), []
-                if self.carry:  # every hop has carry_tracks queries: one group
-                    order = list(range(len(hops)))
-                    results = self._hops(hops, None, order, fused, self._carried(hops))
+                if self.carry:  # every hop has carry_tracks queries: one group, unless the coarse iterations differ
+                    firsts = [self._carry.sched.is_first(sid) for sid, _ in hops]
+                    co = self._carried(hops)
+                    wo = self._carry.warm if self.warm else None
+                    for pos, warm, iters in self._warm_groups(firsts):
+                        results += self._hops(hops, None, pos, fused, co, wo, warm, iters)
+                        order += pos
                 else:
                     qs = [self._query(sid, hop, query_points) for sid, hop in hops]
                     for _, pos in self.sched.group([q.shape[0] for q in qs]):

@@ -633,6 +633,44 @@ int comet_track_carry(const float* tracks, const float* score, const int32_t* id
                       int border, float min_score, float* query, int32_t* ids_out, int32_t* age_out,
                       int32_t* src, int32_t* stats, void* stream);
 
+/* comet_track_warm (DESIGN.md "Warm start"): the coarse tracker's starting coordinates for the n
+ *   hops of a push, one launch, one thread per slot (grid-stride, 256 threads per workgroup, no
+ *   LDS, no atomics, no communication between threads). With stride s < T the previous window has
+ *   already tracked T - s of the new window's T frames; a slot that comet_track_carry carried starts
+ *   on those positions instead of on its query point in every frame.
+ *     prev [n, T, N, 2] f32 pixels: pred_tracks of the previous windows (the `tracks` argument of the
+ *       comet_track_carry call of this push).
+ *     src [n, N] int32, query [n, N, 2] f32 pixels: the outputs of that comet_track_carry call.
+ *     prev_valid [n] int32: as for comet_track_carry; 0 -- prev is not read, every slot is cold.
+ *     s: the stride, 1 <= s <= T - 1. mode: 0 hold, 1 constant velocity.
+ *     div0, div1: the predictor's two divisions (down_ratio, then stride); 1 and 1 when it divides
+ *       by nothing.
+ *   Per hop b and slot j:
+ *   Donor. prev_valid[b] == 0: none. 0 <= src[j] < N: k = src[j] (a carried slot). src[j] =
+ *     INT32_MIN + l with 0 <= l < N (a pad copy): l iff src[l] == l; the lattice pad (src = INT32_MIN
+ *     itself) falls under this with l = 0 and stays cold, since slot 0 is then not carried. Anything
+ *     else (births -M <= src < 0, values outside every range): none. Every index is range-checked
+ *     before it addresses memory.
+ *   Warm row of donor k, in pixels: frame 0 = query[b, j] bit for bit; frame i in [1, T - 1 - s] =
+ *     prev[b, i + s, k]; frame i > T - 1 - s, with e = i - (T - 1 - s), last = prev[b, T - 1, k] and
+ *     before = prev[b, T - 2, k]: hold -- last; velocity -- last + (float)e * (last - before) in f32,
+ *     one rounding per operation (no contraction), then clamped by v < 0 ? 0 : (v > hi ? hi : v) with
+ *     hi = W - 1 for x and H - 1 for y. If any of the row's 2 T values is not finite before the clamp,
+ *     the slot falls back to a cold row (a value of prev that the row does not use may be anything).
+ *   Cold row: query[b, j] in every frame, what the predictor starts from without this kernel.
+ *   Units: every value is divided by div0 and then by div1 in f32 (IEEE division). For divisors that
+ *     are powers of two (the model's 2 and 4) a cold row is bit-identical to torch's q / down_ratio /
+ *     stride; torch multiplies by the reciprocal of a scalar divisor, which can differ in the last bit
+ *     for other divisors.
+ *   Outputs: coords [n, N, T, 2] f32 (the layout the predictor iterates on); warm [n, N] int32: 0 cold,
+ *     1 carried, 2 pad copy of a carried slot, -1 fallen back (a non-finite value).
+ *   COMET_EINVAL before anything is launched, checked in this order: a null pointer, n < 1, N outside
+ *   [1, COMET_CARRY_MAX_TRACKS], T < 2, s outside [1, T - 1], H or W < 1, mode not 0 or 1, div0 or
+ *   div1 not finite or <= 0, prev / query / coords not 8-B aligned. */
+int comet_track_warm(const float* prev, const int32_t* src, const float* query,
+                     const int32_t* prev_valid, int n, int T, int N, int s, int H, int W, int mode,
+                     float div0, float div1, float* coords, int32_t* warm, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Debug support (bounds asserts and a NaN / Inf check mode).
  * comet_count_nonfinite: adds the number of NaN / Inf elements of x (n elements, dtype) to

@@ -40,7 +40,15 @@ Three PoseStream objects take the same frames, alternating hop by hop in one pro
 Also per timed hop of (b) and (c): survivors, born, padded and the mean age, and the largest
 pred_pose_enc difference between (a) and (b) on the same windows (a difference between two query
 sets, not an error against ground truth). Random-init weights and N(0,1) frames: the tracks say little
-about real imagery."""
+about real imagery.
+
+--carry --warm [--warm-iters K[,K...]] [--warm-mode hold|velocity]: the warm start of the coarse tracker
+(comet_track_warm, DESIGN.md "Warm start") joins the alternation: one more PoseStream per K with
+carry=True, detect_every=1, warm=True, warm_iters=K (default: cfg.track_trainit), to be read against
+(b) carry 1. Also the comet_track_warm launch of a hop alone (20 back-to-back launches / 20), per timed
+hop the slots that started warm, and the largest pred_tracks / pred_pose_enc difference between each
+warm stream and (b) on the same frames: a difference between two tracker runs under random-init
+weights, which converge to nothing meaningful, so it is not an accuracy figure."""
 import argparse
 import json
 import os
@@ -179,16 +187,26 @@ def carry_bench(model, args, dev, cfg):
     objs = {"query_fn": PoseStream(model, query_fn=keypoint_query(sp, track_num=N, min_required=N), **kw),
             "carry_1": PoseStream(model, detect_every=1, **ckw),
             "carry_k": PoseStream(model, detect_every=args.detect_every, **ckw)}
+    warm_names = {}
+    if args.warm:
+        for it in ([None] if args.warm_iters is None else [int(v) for v in args.warm_iters.split(",")]):
+            name = f"warm_{'cfg' if it is None else it}"
+            warm_names[name] = it
+            objs[name] = PoseStream(model, detect_every=1, warm=True, warm_mode=args.warm_mode, warm_iters=it, **ckw)
     names = list(objs)
+    carried = names[1:3]
+    wstats = {k: [] for k in warm_names}
+    wdiff = {k: [0.0, 0.0, 0.0] for k in warm_names}  # pred_tracks (all slots, slots with one query), pred_pose_enc
+    tw = []
     for o in objs.values():
         assert o.push(frames[:T - 1]) == []
     times = {k: [] for k in names}
-    stats = {k: [] for k in names[1:]}
+    stats = {k: [] for k in carried}
     tk, err = [], 0.0
     for j in range(args.warmup + args.hops):
         i = j + T - 1
         res = {}
-        for k in names[j % 3:] + names[:j % 3]:  # (no path always runs first)
+        for k in names[j % len(names):] + names[:j % len(names)]:  # (no path always runs first)
             ms, out = _timed(lambda: objs[k].push(frames[i]))
             assert len(out) == 1 and out[0].frame_index == j
             res[k] = (ms, out[0])
@@ -200,12 +218,28 @@ def carry_bench(model, args, dev, cfg):
         nid = tc.next_id.clone()
         ms_k, _ = _timed(lambda: [ops.track_carry(r.pred_tracks[None], r.pred_score[None].float(), tc.ids, tc.age, nid, pv, 1,
                                                   S, S, args.cell, 0, args.min_score, cand, cn) for _ in range(GATHER_REPS)])
+        if args.warm:
+            wc = objs[next(iter(warm_names))]._carry
+            wq = r.pred_tracks[1].contiguous()[None]
+            ms_w, _ = _timed(lambda: [ops.track_warm(r.pred_tracks[None], r.track_src[None], wq, pv, 1, S, S, args.warm_mode,
+                                                     *wc.warm_div) for _ in range(GATHER_REPS)])
         if j >= args.warmup:
             for k in names:
                 times[k].append(res[k][0])
             tk.append(ms_k / GATHER_REPS)
+            if args.warm:
+                tw.append(ms_w / GATHER_REPS)
+            for k in warm_names:
+                a, b = res[k][1], r
+                wstats[k].append(int((a.track_warm > 0).sum()))
+                same = (a.pred_tracks[0] == b.pred_tracks[0]).all(-1)
+                d = (a.pred_tracks - b.pred_tracks).abs()
+                wdiff[k][0] = max(wdiff[k][0], float(d.max()))
+                if bool(same.any()):
+                    wdiff[k][1] = max(wdiff[k][1], float(d[:, same].max()))
+                wdiff[k][2] = max(wdiff[k][2], float((a.pred_pose_enc - b.pred_pose_enc).abs().max()))
             err = max(err, float((res["query_fn"][1].pred_pose_enc - res["carry_1"][1].pred_pose_enc).abs().max()))
-            for k in names[1:]:
+            for k in carried:
                 rr = res[k][1]
                 sv, bn, pd = loop._carry_counts(rr)
                 live = rr.track_ids >= 0
@@ -219,11 +253,23 @@ def carry_bench(model, args, dev, cfg):
     out["track_carry_ms"] = round(statistics.median(tk), 4)
     out["min_track_carry_ms"] = round(min(tk), 4)
     out["track_carry_timing"] = f"device events around {GATHER_REPS} back-to-back launches / {GATHER_REPS}, median over the hops"
-    for k in names[1:]:
+    for k in carried:
         cols = list(zip(*stats[k]))
         out[f"{k}_per_hop_mean"] = dict(zip(("survivors", "born", "padded", "mean_age"),
                                             [round(statistics.mean(c), 2) for c in cols]))
         out[f"{k}_per_hop_min_max_survivors"] = [min(cols[0]), max(cols[0])]
+    if args.warm:
+        out["warm_mode"] = args.warm_mode
+        out["track_warm_ms"] = round(statistics.median(tw), 4)
+        out["min_track_warm_ms"] = round(min(tw), 4)
+        for k, it in warm_names.items():
+            out[f"{k}_warm_slots_per_hop"] = {"mean": round(statistics.mean(wstats[k]), 2), "min": min(wstats[k]),
+                                              "max": max(wstats[k])}
+            out[f"{k}_vs_carry_1"] = {"max_abs_pred_tracks_px": wdiff[k][0],
+                                      "max_abs_pred_tracks_px_slots_with_one_query": wdiff[k][1],
+                                      "max_abs_pose_enc": wdiff[k][2]}
+        out["warm_diff_note"] = ("differences between two tracker runs on the same frames under random-init weights, which "
+                                 "converge to nothing meaningful: not an accuracy figure")
     out.update({"hops": args.hops, "warmup": args.warmup, "max_abs_pose_enc_diff_query_fn_vs_carry_1": err,
                 "pose_enc_diff_note": "a difference between two query sets on the same windows, not an error against ground truth",
                 "data": "synthetic (N(0,1) frames); random-init weights: the track statistics say little about real imagery"})
@@ -245,6 +291,10 @@ def main():
     ap.add_argument("--detect-every", type=int, default=4, help="--carry: the detector period of the third stream")
     ap.add_argument("--min-score", type=float, default=0.0, help="--carry: carry_min_score")
     ap.add_argument("--cell", type=int, default=8, help="--carry: carry_cell")
+    ap.add_argument("--warm", action="store_true", help="--carry: add warm-started streams to the comparison")
+    ap.add_argument("--warm-iters", type=str, default=None,
+                    help="--warm: comma-separated coarse iteration counts, one warm stream each (default: the config's)")
+    ap.add_argument("--warm-mode", type=str, default="hold", choices=("hold", "velocity"), help="--warm: warm_mode")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         print("stream_bench: no GPU", file=sys.stderr)
@@ -257,6 +307,8 @@ def main():
     cfg = load_config()
     torch.manual_seed(0)
     model = instantiate(cfg.MODEL, _recursive_=False, cfg=cfg).to(dev).eval()
+    if args.warm and not args.carry:
+        ap.error("--warm needs --carry")
     if args.carry:
         carry_bench(model, args, dev, cfg)
         return 0
