@@ -94,6 +94,7 @@ class RingTensor(ctypes.Structure):
 RING_MAX_TENSORS = 4  # COMET_RING_MAX_TENSORS
 FUSE_ROW = 20         # COMET_FUSE_ROW: doubles per accumulator row of comet_pose_fuse
 CARRY_MAX_TRACKS, CARRY_MAX_CANDIDATES, CARRY_MAX_CELLS = 4096, 65536, 8192  # COMET_CARRY_MAX_*
+LM_ROW = 12           # COMET_LM_ROW: doubles per accumulator row of comet_landmark_update
 
 # (name, restype, argtypes); every exported symbol of include/comet_hip.h
 _F = ctypes.c_float
@@ -193,6 +194,8 @@ SIGNATURES = {
                                  _INT, _INT, _INT, _INT, _F, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "comet_track_warm": (_INT, [c_vp, c_vp, c_vp, c_vp, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _F, _F, c_vp, c_vp,
                                 c_vp]),
+    "comet_landmark_update": (_INT, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _INT, _INT,
+                                     _INT, _INT, _INT, _INT, _INT, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

@@ -156,6 +156,23 @@ def crop_resize_normalize(frames, box, crop_size, mean=IMAGENET_MEAN, std=IMAGEN
     return out
 
 
+def crop_intrinsics(intr, box, size):
+    """The intrinsics of the pixels crop_resize_normalize produces: intr = (fx, fy, cx, cy) of the full
+    image, box (x0, y0, x1, y1) the crop, size the output side (or (width, height)) -> (fx, fy, cx, cy)
+    of the crop, floats. Pixel-centre convention, as the resampler places its taps (csrc/data.hip
+    resample coefficients: output pixel xx is centred on in0 + (xx + 0.5) * scale, an input pixel x on
+    x + 0.5): x_full = x0 + (x_crop + 0.5) * bw / size - 0.5, so with sx = size / bw
+    fx' = fx sx and cx' = (cx + 0.5 - x0) sx - 0.5, and likewise in y. The box is truncated to ints as
+    crop_resize_normalize truncates it, so both speak of the same crop."""
+    fx, fy, cx, cy = (float(v) for v in intr)
+    x0, y0, x1, y1 = (int(v) for v in box)
+    if x1 <= x0 or y1 <= y0:
+        raise ValueError(f"crop_intrinsics: empty box {tuple(box)}")
+    ow, oh = (size, size) if isinstance(size, (int, float)) else size
+    sx, sy = float(ow) / (x1 - x0), float(oh) / (y1 - y0)
+    return fx * sx, fy * sy, (cx + 0.5 - x0) * sx - 0.5, (cy + 0.5 - y0) * sy - 0.5
+
+
 class YTDataset(torch.utils.data.Dataset):
     """kubric_movif_SFM_dataset_YT.py:94-300 (same constructor and sample fields). Indexing is
     host-only (worker-safe); `images` is produced on `device` by load_images_from_folder or, for

@@ -662,6 +662,53 @@ def _carry_fields(carry):
     return CARRY_FIELDS + (WARM_FIELDS if carry.get("warm") else ())
 
 
+# cfg.stream.landmarks: a second CSV per sequence, one row per valid live landmark of the last hop
+LANDMARK_FIELDS = ("track_id", "x", "y", "z", "n_obs")
+
+
+def _stream_landmarks(cfg, fuse, carry):
+    """cfg.stream.landmarks (default false) / lm_min_obs (3) / lm_min_pivot (1e-8, a guard, not a tuned
+    value) / lm_weight (null or "score") / lm_gate_px (null: no gate) / lm_inverse_rotation (0) -> the
+    landmark keywords of PoseStream / StreamPool without the intrinsics ({} with landmarks off), which
+    depend on the sequence's box (_track_intr). fuse, carry: what _stream_fuse / _stream_carry returned."""
+    if not _get(cfg, "stream.landmarks", False):
+        return {}
+    if not fuse or not carry:
+        raise ValueError("cfg.stream.landmarks needs cfg.stream.fuse and cfg.stream.carry: a landmark is a carried "
+                         "track triangulated from the fused poses")
+    gate = _get(cfg, "stream.lm_gate_px", None)
+    return dict(landmarks=True, lm_min_obs=int(_get(cfg, "stream.lm_min_obs", 3)),
+                lm_min_pivot=float(_get(cfg, "stream.lm_min_pivot", 1e-8)), lm_weight=_get(cfg, "stream.lm_weight", None),
+                lm_gate_px=None if gate is None else float(gate),
+                lm_inverse_rotation=int(_get(cfg, "stream.lm_inverse_rotation", 0)))
+
+
+def _track_intr(dataset, box, size):
+    """(fx, fy, cx, cy) of the pixels the tracks of a sequence live in: the dataset's intrinsics mapped
+    into the crop `box` resized to size x size, the frames stream_eval pushes."""
+    from .data import crop_intrinsics
+    from .models.utils import INTRINSICS
+    return crop_intrinsics(INTRINSICS[dataset], box, size)
+
+
+def landmarks_csv(csv_path):
+    """The path of the landmark CSV that goes with the hop CSV csv_path: <stem>_landmarks.csv."""
+    stem, ext = os.path.splitext(csv_path)
+    return stem + "_landmarks" + ext
+
+
+def _log_landmarks(csv_path, lm, stream=0):
+    """LandmarkMap.snapshot(stream), the valid live landmarks of the stream's last hop, as
+    landmarks_csv(csv_path): one row per landmark (LANDMARK_FIELDS; x, y, z in the body frame), the
+    header alone when there is none. -> number of rows."""
+    logger = CsvLogger(landmarks_csv(csv_path), LANDMARK_FIELDS)
+    ids, X, n_obs = lm.snapshot(stream)
+    rows = torch.cat([ids.double()[:, None], X.double(), n_obs.double()[:, None]], 1).tolist()
+    for i, x, y, z, k in rows:
+        logger.log(dict(zip(LANDMARK_FIELDS, (int(i), x, y, z, int(k)))))
+    return len(rows)
+
+
 def _carry_counts(r):
     """(survivors, born, padded) of a carried StreamResult, from track_src (ops.CarryOut)."""
     src = r.track_src.tolist()
@@ -724,7 +771,12 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
     be None, and the CSV gains the trailing columns survivors, born, padded. Off: the CSV is what it was.
     cfg.stream.warm (default false; needs cfg.stream.carry; with warm_mode "hold" / "velocity" and warm_iters,
     default cfg.track_trainit) starts the coarse tracker of every hop but the first from the previous
-    window's tracks (PoseStream warm=True); the CSV gains a last column warm, the slots that started so."""
+    window's tracks (PoseStream warm=True); the CSV gains a last column warm, the slots that started so.
+    cfg.stream.landmarks (default false; needs fuse and carry; with lm_min_obs, lm_min_pivot, lm_weight,
+    lm_gate_px and lm_inverse_rotation) turns the landmark map on (PoseStream landmarks=True) with the
+    intrinsics of the anchor's dataset mapped into `box` (data.crop_intrinsics); the hop CSV is what it
+    was, and at the end of the stream landmarks_csv(csv_path) takes the final snapshot, one row per valid
+    live landmark (LANDMARK_FIELDS)."""
     from .data import crop_resize_normalize
     from .stream import PoseStream, keypoint_query
     if not _get(cfg, "stream.enable", False):
@@ -739,10 +791,13 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
         query_fn = keypoint_query(sp, sift=sift, track_num=_get(cfg, "train.track_num", 512))
     mp = _get(cfg, "mixed_precision", "no")
     fuse, fuse_weight, anchor, fields = _stream_fuse(cfg, anchor)
+    lm = _stream_landmarks(cfg, fuse, carry)
+    if lm:
+        lm["track_intr"] = _track_intr(anchor[4], box, size)
     stream = PoseStream(model, window=window, stride=int(_get(cfg, "stream.stride", 1)),
                         capacity=_get(cfg, "stream.capacity", None), query_fn=query_fn, anchor=anchor,
                         precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight,
-                        **carry)
+                        **carry, **lm)
     if carry:
         fields = tuple(fields) + _carry_fields(carry)
     logger = CsvLogger(csv_path, fields)
@@ -759,6 +814,8 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
             hops += 1
     if fuse and last is not None:
         _log_hop(logger, fields, last[0], window, None, last=last[1])
+    if lm:
+        _log_landmarks(csv_path, stream.landmark_map)
     return hops
 
 
@@ -776,7 +833,9 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
     when a sequence ends (all hops of a push are fused by one launch; every anchor must then carry
     one ratio and one dataset). cfg.stream.carry and candidate_fn: as stream_eval (StreamPool
     carry=True; a sequence that takes over a stream starts with fresh ids). cfg.stream.warm, warm_mode and
-    warm_iters: as stream_eval (StreamPool warm=True)."""
+    warm_iters: as stream_eval (StreamPool warm=True). cfg.stream.landmarks and lm_*: as stream_eval
+    (StreamPool landmarks=True): a sequence that takes over a stream brings the intrinsics of its own box
+    and starts with an empty map, and when it ends csv_dir/<name>_landmarks.csv takes its final snapshot."""
     from .data import crop_resize_normalize
     from .stream import StreamPool, keypoint_query
     if not _get(cfg, "stream.enable", False):
@@ -796,11 +855,15 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
     anchored = fuse or bool(anchors)
     if anchored and default_anchor is None:
         raise ValueError("stream_eval_pool: anchors without cfg.stream.fuse are not supported")
+    lm = _stream_landmarks(cfg, fuse, carry)
+    if lm:  # (the uncropped intrinsics stand in until reset(sid, track_intr=...) brings each sequence's own)
+        from .models.utils import INTRINSICS
+        lm["track_intrs"] = [INTRINSICS[default_anchor[4]]] * S
     pool = StreamPool(model, streams=S, window=window, stride=int(_get(cfg, "stream.stride", 1)),
                       capacity=_get(cfg, "stream.capacity", None), query_fn=query_fn,
                       anchors=[default_anchor] * S if fuse else None,
                       precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight,
-                      **carry)
+                      **carry, **lm)
     if carry:
         fields = tuple(fields) + _carry_fields(carry)
     lasts = {}  # stream id -> (last result, its row): flushed when the sequence ends
@@ -817,7 +880,8 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
                 if nxt is None:
                     return None
                 name, frames_iter, box = nxt
-                pool.reset(sid, anchor=anchors.get(name, default_anchor) if fuse else None)
+                pool.reset(sid, anchor=anchors.get(name, default_anchor) if fuse else None,
+                           track_intr=_track_intr(default_anchor[4], box, size) if lm else None)
                 running[sid] = (name, iter(frames_iter), box, CsvLogger(os.path.join(csv_dir, f"{name}.csv"), fields))
                 hops[name] = 0
             frame = next(running[sid][1], None)
@@ -826,6 +890,8 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
             if fuse and sid in lasts:
                 r, row = lasts.pop(sid)
                 _log_hop(running[sid][3], fields, r, window, None, last=row)
+            if lm:
+                _log_landmarks(running[sid][3].path, pool.landmark_map, sid)
             del running[sid]
 
     while True:

@@ -784,6 +784,54 @@ def track_warm(prev, src, query, prev_valid, s, H, W, mode, div0, div1):
     return out
 
 
+class LandmarkOut(NamedTuple):
+    X: torch.Tensor       # [n, N, 3] f64 landmarks in the body frame (0 where state != 1)
+    n_obs: torch.Tensor   # [n, N] int32 frames the landmark has been seen in
+    err_px: torch.Tensor  # [n, N] f32 reprojection error on window position s (+inf where state != 1)
+    state: torch.Tensor   # [n, N] int32: 1 valid, 0 none, 2 ill-conditioned, 3 behind the camera, -1 not finite
+
+
+def landmark_update(tracks, R, T, ids, src, stream_idx, stream_idx_host, intr, intr_host, acc, acc_id, s,
+                    weights=None, inverse_rotation=0, min_obs=3, min_pivot=1e-8):
+    """comet_landmark_update (include/comet_hip.h): the n hops tracks [n, T, N, 2] f32 with the fused
+    poses R [n, T, 4] f32 / T [n, T, 3] f64 and the ids / src [n, N] int32 of ops.track_carry update the
+    landmark state acc [rows, 12] f64 / acc_id [rows] int32 in place -> LandmarkOut, all in one launch.
+    stream_idx [n] int32 and intr [n, 4] f64 on the device, *_host the same values as ctypes arrays
+    (int32 * n, double * 4n; checked by the library before it launches); weights [n, T, N] f32 or None."""
+    _req_cuda(tracks, R, T, ids, src, stream_idx, intr, acc, acc_id, weights)
+    if tracks.dim() != 4 or tracks.shape[3] != 2 or tracks.dtype != torch.float32 or not tracks.is_contiguous():
+        raise L.CometHipError(f"landmark_update: tracks must be a dense f32 [n, T, N, 2] tensor, got "
+                              f"{tuple(tracks.shape)} {tracks.dtype}")
+    n, Tw, N = tracks.shape[:3]
+    for name, t, shape, dtype in (("R", R, (n, Tw, 4), torch.float32), ("T", T, (n, Tw, 3), torch.float64),
+                                  ("ids", ids, (n, N), torch.int32), ("src", src, (n, N), torch.int32),
+                                  ("stream_idx", stream_idx, (n,), torch.int32), ("intr", intr, (n, 4), torch.float64),
+                                  ("weights", weights, (n, Tw, N), torch.float32)):
+        if t is not None and (t.shape != shape or t.dtype != dtype or not t.is_contiguous()):
+            raise L.CometHipError(f"landmark_update: {name} must be a dense {dtype} {list(shape)} tensor")
+    if acc.dim() != 2 or acc.shape[1] != L.LM_ROW or acc.dtype != torch.float64 or not acc.is_contiguous():
+        raise L.CometHipError(f"landmark_update: acc must be a dense f64 [rows, {L.LM_ROW}] tensor")
+    if acc_id.shape != (acc.shape[0],) or acc_id.dtype != torch.int32 or not acc_id.is_contiguous():
+        raise L.CometHipError("landmark_update: acc_id must be a dense int32 [rows] tensor")
+    if len(stream_idx_host) != n or len(intr_host) != 4 * n:
+        raise L.CometHipError("landmark_update: stream_idx_host needs n entries and intr_host 4 n")
+    dev = tracks.device
+    if any(t is not None and t.device != dev for t in (R, T, ids, src, stream_idx, intr, acc, acc_id, weights)):
+        raise L.CometHipError("landmark_update: every tensor must be on one device")
+    out = LandmarkOut(torch.empty(n, N, 3, device=dev, dtype=torch.float64),
+                      torch.empty(n, N, device=dev, dtype=torch.int32), torch.empty(n, N, device=dev),
+                      torch.empty(n, N, device=dev, dtype=torch.int32))
+    e0 = PROF.start()
+    L.check(L.load().comet_landmark_update(_p(tracks), _p(weights), _p(R), _p(T), _p(ids), _p(src), _p(stream_idx),
+                                           ctypes.addressof(stream_idx_host), _p(intr), ctypes.addressof(intr_host),
+                                           _p(acc), _p(acc_id), acc.shape[0], n, Tw, N, int(s), int(inverse_rotation),
+                                           int(min_obs), float(min_pivot), *[_p(t) for t in out], stream()),
+            "landmark_update")
+    if e0 is not None:
+        PROF.stop(e0, "comet_landmark_update", 0.0, float(n * N * (2 * 8 * L.LM_ROW + (s + 1) * 8 + 8 + 40)))
+    return out
+
+
 def resize_bilinear_pool(x, oh, ow):
     """NHWC x [n, h, w, c] -> (y [n, oh, ow, c] bilinear, align_corners=True; its 2 x 2 average
     pool [n, oh // 2, ow // 2, c]) in one kernel: resize_bilinear + avgpool2_nhwc bit for bit."""

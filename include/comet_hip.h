@@ -671,6 +671,49 @@ int comet_track_warm(const float* prev, const int32_t* src, const float* query,
                      const int32_t* prev_valid, int n, int T, int N, int s, int H, int W, int mode,
                      float div0, float div1, float* coords, int32_t* warm, void* stream);
 
+/* comet_landmark_update (DESIGN.md "Landmarks"): a carried track, seen over the frames whose fused
+ *   pose is final, is a multi-view triangulation problem; this keeps its normal equations and returns
+ *   a 3-D point in the body frame for every query slot of the n hops of a push, one launch, one thread
+ *   per (hop h, slot j), grid (ceil(N / 256), n), no LDS, no atomics, no communication between threads.
+ *   Everything is IEEE double evaluated as written (no contraction).
+ *   State: acc [rows, COMET_LM_ROW] f64 and acc_id [rows] int32, rows = streams * N; the row of slot j
+ *   of the stream of hop h is stream_idx[h] * N + j. Row layout:
+ *     0..5 upper triangle of M = sum w a a^T (xx xy xz yy yz zz) | 6..8 g = sum w a c | 9 sum w c^2 |
+ *     10 frames added | 11 zero.
+ *   Inputs per hop: tracks [n, T, N, 2] f32 pixels (pred_tracks); weights [n, T, N] f32 or NULL (= 1);
+ *     R [n, T, 4] f32 quaternions (w first) and T [n, T, 3] f64, the fused_R / fused_T of
+ *     comet_pose_fuse; ids, src [n, N] int32 as comet_track_carry returned them for this hop;
+ *     intr [n, 4] f64 = (fx, fy, cx, cy) of the pixels the tracks live in.
+ *   Observation of the frame at window position i: Rm = the matrix of R[h, i] (the formula of
+ *     minipytorch3d.quaternion_to_matrix; its transpose when inverse_rotation = 1), rows r1 r2 r3,
+ *     x_cam = Rm X + T. With xn = (x - cx) / fx, yn = (y - cy) / fy the two equations a . X = c are
+ *     a = r1 - xn r3, c = xn tz - tx and a = r2 - yn r3, c = yn tz - ty, each added with weight w. A frame
+ *     whose x, y or w is not finite, or whose w <= 0, adds nothing.
+ *   Frames: a hop commits the positions [0, s), s = stride: the frames that leave the window after this
+ *     hop, whose fused pose is final; every frame of a stream is committed exactly once.
+ *   Reset rule: ids[j] < 0 (a pad): the row is zeroed, acc_id = -1, state 0. src[j] != j (born) or
+ *     acc_id[row] != ids[j]: the row is overwritten by this hop's observations, acc_id = ids[j]. Otherwise
+ *     the observations are added.
+ *   Solve, after the update: M X = g by an unpivoted LDL^T. Outputs per (h, j): X [3] f64; n_obs int32;
+ *     err_px f32, the pixel distance between tracks[h, s, j] and the projection of X with the pose of
+ *     position s (the frame that becomes the next window's first); state int32: 1 valid | 0 no landmark
+ *     (a pad, or n_obs < min_obs) | 2 ill-conditioned (a pivot <= min_pivot * max(diag M)) | 3 behind the
+ *     camera (r3 . X + tz <= 0 at position s) | -1 a non-finite X or err_px. For every state other than 1,
+ *     X is 0 and err_px is +inf.
+ *   COMET_EINVAL before anything is launched, checked in this order: a null pointer (weights may be
+ *   null), n < 1, N outside [1, 4096], T < 2, s outside [1, T - 1], rows < n * N, a host stream index
+ *   outside [0, rows / N) or two equal ones (two hops on one row would race; a stream completes at most
+ *   one hop per push), host intrinsics whose fx or fy is not finite and positive, inverse_rotation not 0
+ *   or 1, min_obs < 2, min_pivot outside [0, 1), tracks / T / intr / X not 8-B aligned or R / acc not
+ *   16-B aligned. The kernel range-checks every row index before it addresses memory. */
+#define COMET_LM_ROW 12
+int comet_landmark_update(const float* tracks, const float* weights, const float* R, const double* T,
+                          const int32_t* ids, const int32_t* src, const int32_t* stream_idx,
+                          const int32_t* stream_idx_host, const double* intr, const double* intr_host,
+                          double* acc, int32_t* acc_id, int rows, int n, int Tw, int N, int s,
+                          int inverse_rotation, int min_obs, double min_pivot, double* X, int32_t* n_obs,
+                          float* err_px, int32_t* state, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Debug support (bounds asserts and a NaN / Inf check mode).
  * comet_count_nonfinite: adds the number of NaN / Inf elements of x (n elements, dtype) to
