@@ -95,6 +95,7 @@ RING_MAX_TENSORS = 4  # COMET_RING_MAX_TENSORS
 FUSE_ROW = 20         # COMET_FUSE_ROW: doubles per accumulator row of comet_pose_fuse
 CARRY_MAX_TRACKS, CARRY_MAX_CANDIDATES, CARRY_MAX_CELLS = 4096, 65536, 8192  # COMET_CARRY_MAX_*
 LM_ROW = 12           # COMET_LM_ROW: doubles per accumulator row of comet_landmark_update
+PNP_MAX_ITERS = 16    # COMET_PNP_MAX_ITERS: Gauss-Newton steps of comet_landmark_pnp
 
 # (name, restype, argtypes); every exported symbol of include/comet_hip.h
 _F = ctypes.c_float
@@ -196,6 +197,10 @@ SIGNATURES = {
                                 c_vp]),
     "comet_landmark_update": (_INT, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _INT, _INT,
                                      _INT, _INT, _INT, _INT, _INT, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "comet_landmark_pnp": (_INT, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _INT, _INT, _INT, _INT, _INT, _INT,
+                                  ctypes.c_double, _INT, ctypes.c_double, c_vp, _INT, c_vp, c_vp, ctypes.c_double,
+                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

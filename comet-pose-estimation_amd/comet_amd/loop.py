@@ -683,6 +683,40 @@ def _stream_landmarks(cfg, fuse, carry):
                 lm_inverse_rotation=int(_get(cfg, "stream.lm_inverse_rotation", 0)))
 
 
+# cfg.stream.pnp: a third CSV per sequence, one row per hop for the frame that becomes the next window's first
+PNP_FIELDS = ("hop", "frame", "state", "inliers", "rms_px", "qw", "qx", "qy", "qz", "tx", "ty", "tz")
+
+
+def _stream_pnp(cfg, lm):
+    """cfg.stream.pnp (default false) / pnp_iters (4, a stated number of steps, not a tuned value) /
+    pnp_huber_px (required with pnp: nothing here derives one) / pnp_min_pts (6) / pnp_weight (0: report
+    only) -> the PnP keywords of PoseStream / StreamPool ({} with pnp off). lm: what _stream_landmarks
+    returned."""
+    if not _get(cfg, "stream.pnp", False):
+        return {}
+    if not lm:
+        raise ValueError("cfg.stream.pnp needs cfg.stream.landmarks: a frame is posed against the landmark map")
+    huber = _get(cfg, "stream.pnp_huber_px", None)
+    if huber is None:
+        raise ValueError("cfg.stream.pnp needs cfg.stream.pnp_huber_px, the Huber threshold in pixels")
+    return dict(pnp=True, pnp_iters=int(_get(cfg, "stream.pnp_iters", 4)), pnp_huber_px=float(huber),
+                pnp_min_pts=int(_get(cfg, "stream.pnp_min_pts", 6)), pnp_weight=float(_get(cfg, "stream.pnp_weight", 0.0)))
+
+
+def pnp_csv(csv_path):
+    """The path of the PnP CSV that goes with the hop CSV csv_path: <stem>_pnp.csv."""
+    stem, ext = os.path.splitext(csv_path)
+    return stem + "_pnp" + ext
+
+
+def _log_pnp(logger, hop, r, stride):
+    """One row of the PnP CSV (PNP_FIELDS): window position `stride` of the hop's StreamResult, the frame
+    that becomes the next window's first (the input pose, with state != 1, where nothing was solved)."""
+    i = int(stride)
+    vals = [hop, r.frame_index + i, int(r.pnp_state[i]), int(r.pnp_inliers[i]), float(r.pnp_rms_px[i])]
+    logger.log(dict(zip(PNP_FIELDS, vals + r.pnp_R[i].double().tolist() + r.pnp_T[i].double().tolist())))
+
+
 def _track_intr(dataset, box, size):
     """(fx, fy, cx, cy) of the pixels the tracks of a sequence live in: the dataset's intrinsics mapped
     into the crop `box` resized to size x size, the frames stream_eval pushes."""
@@ -792,15 +826,17 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
     mp = _get(cfg, "mixed_precision", "no")
     fuse, fuse_weight, anchor, fields = _stream_fuse(cfg, anchor)
     lm = _stream_landmarks(cfg, fuse, carry)
+    pnp = _stream_pnp(cfg, lm)
     if lm:
         lm["track_intr"] = _track_intr(anchor[4], box, size)
     stream = PoseStream(model, window=window, stride=int(_get(cfg, "stream.stride", 1)),
                         capacity=_get(cfg, "stream.capacity", None), query_fn=query_fn, anchor=anchor,
                         precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight,
-                        **carry, **lm)
+                        **carry, **lm, **pnp)
     if carry:
         fields = tuple(fields) + _carry_fields(carry)
     logger = CsvLogger(csv_path, fields)
+    pnp_logger = CsvLogger(pnp_csv(csv_path), PNP_FIELDS) if pnp else None
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     hops, last = 0, None
     for frame in frames_iter:
@@ -811,6 +847,8 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
         for r in results:
             e1.synchronize()
             last = (r, _log_hop(logger, fields, r, window, e0.elapsed_time(e1)))
+            if pnp:
+                _log_pnp(pnp_logger, hops, r, stream.landmark_map.stride)
             hops += 1
     if fuse and last is not None:
         _log_hop(logger, fields, last[0], window, None, last=last[1])
@@ -856,6 +894,7 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
     if anchored and default_anchor is None:
         raise ValueError("stream_eval_pool: anchors without cfg.stream.fuse are not supported")
     lm = _stream_landmarks(cfg, fuse, carry)
+    pnp = _stream_pnp(cfg, lm)
     if lm:  # (the uncropped intrinsics stand in until reset(sid, track_intr=...) brings each sequence's own)
         from .models.utils import INTRINSICS
         lm["track_intrs"] = [INTRINSICS[default_anchor[4]]] * S
@@ -863,9 +902,10 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
                       capacity=_get(cfg, "stream.capacity", None), query_fn=query_fn,
                       anchors=[default_anchor] * S if fuse else None,
                       precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight,
-                      **carry, **lm)
+                      **carry, **lm, **pnp)
     if carry:
         fields = tuple(fields) + _carry_fields(carry)
+    pnp_loggers = {}  # sequence name -> the logger of its <name>_pnp.csv
     lasts = {}  # stream id -> (last result, its row): flushed when the sequence ends
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     seqs = iter(sequences)
@@ -884,6 +924,8 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
                            track_intr=_track_intr(default_anchor[4], box, size) if lm else None)
                 running[sid] = (name, iter(frames_iter), box, CsvLogger(os.path.join(csv_dir, f"{name}.csv"), fields))
                 hops[name] = 0
+                if pnp:
+                    pnp_loggers[name] = CsvLogger(pnp_csv(running[sid][3].path), PNP_FIELDS)
             frame = next(running[sid][1], None)
             if frame is not None:
                 return frame
@@ -907,6 +949,8 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
             e1.synchronize()
             name, logger = running[sid][0], running[sid][3]
             lasts[sid] = (r, _log_hop(logger, fields, r, window, e0.elapsed_time(e1)))
+            if pnp:
+                _log_pnp(pnp_loggers[name], hops[name], r, pool.landmark_map.stride)
             hops[name] += 1
 
 

@@ -832,6 +832,68 @@ def landmark_update(tracks, R, T, ids, src, stream_idx, stream_idx_host, intr, i
     return out
 
 
+class PnpOut(NamedTuple):
+    q: torch.Tensor       # [n, T, 4] f64 refined rotation (unit quaternion, w >= 0; the input where state != 1)
+    R: torch.Tensor       # [n, T, 4] f32, q rounded (the input bit for bit where state != 1)
+    T: torch.Tensor       # [n, T, 3] f64 refined translation (the input bit for bit where state != 1)
+    inliers: torch.Tensor  # [n, T] int32 usable points within huber_px at the refined pose
+    rms_px: torch.Tensor  # [n, T] f32 weighted rms reprojection error (+inf where state != 1)
+    state: torch.Tensor   # [n, T] int32: 1 solved, 0 too few usable points, 2 degenerate, -1 not finite
+
+
+def landmark_pnp(tracks, X, state, R, T, intr, intr_host, s, huber_px, weights=None, inverse_rotation=0, iters=4,
+                 min_pts=6, min_pivot=1e-8, fuse_acc=None, slots=None, slots_host=None, inject_w=0.0, fuse_intr=None):
+    """comet_landmark_pnp (include/comet_hip.h): every frame of the n hops tracks [n, T, N, 2] f32 is posed
+    against the landmarks X [n, N, 3] f64 / state [n, N] int32 (ops.landmark_update of the same push) by
+    `iters` Gauss-Newton steps from the fused pose R [n, T, 4] f32 / T [n, T, 3] f64 -> PnpOut, one launch.
+    intr [n, 4] f64 on the device, intr_host the same values as a ctypes double array; weights [n, T, N]
+    f32 or None. With fuse_acc [rows, 20] f64 (ops.pose_fuse's accumulator), its slots [n * T] int32 /
+    slots_host of the same push, fuse_intr = the fuser's (fx, fy, cx, cy) and inject_w > 0, the solved poses
+    of the positions [s, T) are added to their rows as one hypothesis of weight inject_w each."""
+    _req_cuda(tracks, X, state, R, T, intr, weights, fuse_acc, slots)
+    if tracks.dim() != 4 or tracks.shape[3] != 2 or tracks.dtype != torch.float32 or not tracks.is_contiguous():
+        raise L.CometHipError(f"landmark_pnp: tracks must be a dense f32 [n, T, N, 2] tensor, got "
+                              f"{tuple(tracks.shape)} {tracks.dtype}")
+    n, Tw, N = tracks.shape[:3]
+    for name, t, shape, dtype in (("X", X, (n, N, 3), torch.float64), ("state", state, (n, N), torch.int32),
+                                  ("R", R, (n, Tw, 4), torch.float32), ("T", T, (n, Tw, 3), torch.float64),
+                                  ("intr", intr, (n, 4), torch.float64),
+                                  ("weights", weights, (n, Tw, N), torch.float32)):
+        if t is not None and (t.shape != shape or t.dtype != dtype or not t.is_contiguous()):
+            raise L.CometHipError(f"landmark_pnp: {name} must be a dense {dtype} {list(shape)} tensor")
+    if len(intr_host) != 4 * n:
+        raise L.CometHipError("landmark_pnp: intr_host needs 4 n entries")
+    rows, fi = 0, (0.0, 0.0, 0.0, 0.0)
+    if fuse_acc is not None:
+        if fuse_acc.dim() != 2 or fuse_acc.shape[1] != L.FUSE_ROW or fuse_acc.dtype != torch.float64 or \
+                not fuse_acc.is_contiguous():
+            raise L.CometHipError(f"landmark_pnp: fuse_acc must be a dense f64 [rows, {L.FUSE_ROW}] tensor")
+        if slots is None or slots_host is None or slots.dtype != torch.int32 or slots.numel() != n * Tw or \
+                not slots.is_contiguous() or len(slots_host) != n * Tw:
+            raise L.CometHipError(f"landmark_pnp: fuse_acc needs slots, a dense int32 device tensor of {n * Tw} entries "
+                                  "with a host copy of the same length")
+        if fuse_intr is None or len(fuse_intr) != 4:
+            raise L.CometHipError("landmark_pnp: fuse_acc needs fuse_intr = (fx, fy, cx, cy)")
+        rows, fi = fuse_acc.shape[0], tuple(float(v) for v in fuse_intr)
+    else:
+        slots = slots_host = None
+    dev = tracks.device
+    if any(t is not None and t.device != dev for t in (X, state, R, T, intr, weights, fuse_acc, slots)):
+        raise L.CometHipError("landmark_pnp: every tensor must be on one device")
+    out = PnpOut(torch.empty(n, Tw, 4, device=dev, dtype=torch.float64), torch.empty(n, Tw, 4, device=dev),
+                 torch.empty(n, Tw, 3, device=dev, dtype=torch.float64), torch.empty(n, Tw, device=dev, dtype=torch.int32),
+                 torch.empty(n, Tw, device=dev), torch.empty(n, Tw, device=dev, dtype=torch.int32))
+    e0 = PROF.start()
+    L.check(L.load().comet_landmark_pnp(_p(tracks), _p(weights), _p(X), _p(state), _p(R), _p(T), _p(intr),
+                                        ctypes.addressof(intr_host), n, Tw, N, int(s), int(inverse_rotation), int(iters),
+                                        float(huber_px), int(min_pts), float(min_pivot), _p(fuse_acc), rows, _p(slots),
+                                        None if slots_host is None else ctypes.addressof(slots_host), float(inject_w),
+                                        *fi, *[_p(t) for t in out], stream()), "landmark_pnp")
+    if e0 is not None:
+        PROF.stop(e0, "comet_landmark_pnp", 0.0, float(n * Tw * (int(iters) + 1) * N * (24 + 4 + 8 + 4)))
+    return out
+
+
 def resize_bilinear_pool(x, oh, ow):
     """NHWC x [n, h, w, c] -> (y [n, oh, ow, c] bilinear, align_corners=True; its 2 x 2 average
     pool [n, oh // 2, ow // 2, c]) in one kernel: resize_bilinear + avgpool2_nhwc bit for bit."""

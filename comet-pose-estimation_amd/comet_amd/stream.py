@@ -115,6 +115,12 @@ class StreamResult(_StreamFields):
     landmark_obs: Optional[torch.Tensor] = None    # [N] int32 frames the landmark has been seen in
     landmark_err: Optional[torch.Tensor] = None    # [N] f32 reprojection error in pixels on position `stride`
     landmark_state: Optional[torch.Tensor] = None  # [N] int32: 1 valid, 0 none, 2 ill-conditioned, 3 behind, -1 not finite
+    # pnp=True only (LandmarkMap.pnp): every frame of the window posed against the landmark map
+    pnp_R: Optional[torch.Tensor] = None        # [T, 4] f32 quaternion (fused_R where pnp_state != 1)
+    pnp_T: Optional[torch.Tensor] = None        # [T, 3] float64 (fused_T where pnp_state != 1)
+    pnp_inliers: Optional[torch.Tensor] = None  # [T] int32 landmarks within pnp_huber_px at the refined pose
+    pnp_rms_px: Optional[torch.Tensor] = None   # [T] f32 weighted rms reprojection error (+inf where pnp_state != 1)
+    pnp_state: Optional[torch.Tensor] = None    # [T] int32: 1 solved, 0 too few landmarks, 2 degenerate, -1 not finite
 
     def _replace(self, **kw):
         r = super()._replace(**kw)
@@ -130,6 +136,12 @@ class StreamResult(_StreamFields):
         """The result with row b of an ops.LandmarkOut."""
         r = self._replace()
         r.landmarks, r.landmark_obs, r.landmark_err, r.landmark_state = lo.X[b], lo.n_obs[b], lo.err_px[b], lo.state[b]
+        return r
+
+    def with_pnp(self, po, b):
+        """The result with row b of an ops.PnpOut."""
+        r = self._replace()
+        r.pnp_R, r.pnp_T, r.pnp_inliers, r.pnp_rms_px, r.pnp_state = po.R[b], po.T[b], po.inliers[b], po.rms_px[b], po.state[b]
         return r
 
 
@@ -576,6 +588,24 @@ def _check_landmarks(landmarks, fuse, carry, intrs, streams, lm_weight, lm_gate_
         raise ValueError(f"lm_gate_px must be None or a distance in pixels >= 0, got {lm_gate_px}")
 
 
+def _check_pnp(pnp, landmarks, pnp_iters, pnp_huber_px, pnp_min_pts, pnp_weight):
+    """-> the keywords of LandmarkMap.pnp, or None with pnp off."""
+    if not pnp:
+        return None
+    if not landmarks:
+        raise ValueError("pnp=True needs landmarks=True: a frame is posed against the landmark map")
+    if pnp_huber_px is None or not 0.0 < float(pnp_huber_px) < float("inf"):
+        raise ValueError(f"pnp=True needs pnp_huber_px, a finite distance in pixels > 0 (nothing here derives one), got "
+                         f"{pnp_huber_px}")
+    if not 1 <= int(pnp_iters) <= L.PNP_MAX_ITERS:
+        raise ValueError(f"pnp_iters must be 1 to {L.PNP_MAX_ITERS}, got {pnp_iters}")
+    if int(pnp_min_pts) < 4:
+        raise ValueError(f"pnp_min_pts must be at least 4, got {pnp_min_pts}")
+    if not 0.0 <= float(pnp_weight) < float("inf"):
+        raise ValueError(f"pnp_weight must be finite and >= 0, got {pnp_weight}")
+    return dict(iters=int(pnp_iters), huber_px=float(pnp_huber_px), min_pts=int(pnp_min_pts), weight=float(pnp_weight))
+
+
 def gate_scores(score, state, err_px, s, gate_px):
     """lm_gate_px: pred_score [n, T, N] -> a copy whose row s is -inf where the slot's landmark is valid
     (state == 1) and its reprojection error exceeds gate_px; every other entry is the input's. The track
@@ -586,18 +616,26 @@ def gate_scores(score, state, err_px, s, gate_px):
     return out
 
 
-def _landmark_step(lm, sids, tr, sc, fo, ids, src, lm_weight, lm_gate_px):
+def _landmark_step(lm, sids, tr, sc, fo, ids, src, lm_weight, lm_gate_px, pnp=None, fuser=None, hops=None):
     """The landmark launch of a push: the hops of `sids` with pred_tracks tr [n, T, N, 2], pred_score sc
     [n, T, N], their ops.FuseOut rows fo and the carry's ids / src [n, N] -> (ops.LandmarkOut, the score
-    TrackCarry.update takes: sc itself, or its gated copy when lm_gate_px is given)."""
+    TrackCarry.update takes: sc itself, or its gated copy when lm_gate_px is given, the ops.PnpOut or None).
+    pnp (_check_pnp): the PnP launch follows on the same rows, with the landmark launch's weights; with
+    pnp["weight"] > 0 it adds its poses to the accumulator of `fuser`, on the rows of `hops` = [(stream, Hop)],
+    the hops fo was fused from, in its order."""
     if tr is None or sc is None:
         raise RuntimeError("landmarks need the model's pred_tracks and pred_score outputs")
     n, T = tr.shape[:2]
     w = sc.float().contiguous() if lm_weight == "score" else None
-    lo = lm.update(sids, tr.float().contiguous(), fo.R.view(n, T, 4), fo.T.view(n, T, 3), ids, src, w)
+    trf, R, Tx = tr.float().contiguous(), fo.R.view(n, T, 4), fo.T.view(n, T, 3)
+    lo = lm.update(sids, trf, R, Tx, ids, src, w)
+    po = None
+    if pnp is not None:
+        po = lm.pnp(sids, trf, R, Tx, lo, w, fuser if pnp["weight"] > 0.0 else None, hops, iters=pnp["iters"],
+                    huber_px=pnp["huber_px"], min_pts=pnp["min_pts"], weight=pnp["weight"])
     if lm_gate_px is not None:
         sc = gate_scores(sc, lo.state, lo.err_px, lm.stride, lm_gate_px)
-    return lo, sc
+    return lo, sc, po
 
 
 class LandmarkMap:
@@ -706,6 +744,35 @@ class LandmarkMap:
             self._last[s] = (out, b, ids)
         return out
 
+    def pnp(self, sids, tracks, R, T, lo, weights=None, fuser=None, hops=None, iters=4, huber_px=None, min_pts=6,
+            weight=0.0):
+        """Every frame of the hops of `sids` posed against the landmarks of the same push (DESIGN.md "PnP
+        refinement"): tracks [n, T, N, 2] f32, R [n, T, 4] f32 / T [n, T, 3] f64 the fused poses, lo the
+        ops.LandmarkOut update() returned for these hops, weights [n, T, N] f32 or None -> ops.PnpOut, one
+        comet_landmark_pnp launch. `iters` Gauss-Newton steps with the Huber threshold huber_px (required;
+        nothing here derives one); fewer than min_pts usable landmarks leave a frame's pose as it came.
+        With a PoseFuser and weight > 0 the solved poses of the positions [stride, T) are added to the
+        fuser's accumulator as one hypothesis of that weight each; `hops` = [(stream, Hop)], the hops of
+        that push's fuser.fuse() call in its order, then name the rows (the fuser's own slot table)."""
+        sids = tuple(self._id(s) for s in sids)
+        if len(sids) == 0 or len(set(sids)) != len(sids):
+            raise ValueError(f"pnp takes at least one hop and one hop per stream, got the streams {list(sids)}")
+        if huber_px is None:
+            raise ValueError("pnp needs huber_px, the Huber threshold in pixels")
+        if lo.X.shape[0] != len(sids):
+            raise ValueError(f"{len(sids)} hops need the LandmarkOut of the same {len(sids)} hops, got {lo.X.shape[0]} rows")
+        self._ensure(tracks.device)
+        _, _, intr, intr_host = self._table(sids)
+        kw = {}
+        if fuser is not None and weight > 0.0:
+            if hops is None or tuple(int(s) for s, _ in hops) != sids:
+                raise ValueError(f"the feedback needs hops, the (stream, Hop) pairs of the streams {list(sids)} in this "
+                                 f"order, got {None if hops is None else [int(s) for s, _ in hops]}")
+            slots, slots_host = fuser._table(fuser.ring.table(list(hops)))
+            kw = dict(fuse_acc=fuser.acc, slots=slots, slots_host=slots_host, inject_w=weight, fuse_intr=fuser.intr)
+        return ops.landmark_pnp(tracks, lo.X, lo.state, R, T, intr, intr_host, self.stride, huber_px, weights,
+                                self.inverse_rotation, iters, min_pts, self.min_pivot, **kw)
+
     def snapshot(self, stream=0):
         """(ids [L] int32, X [L, 3] float64, n_obs [L] int32) of the stream's valid live landmarks, as its
         last hop left them (empty before the first hop and after a reset)."""
@@ -792,15 +859,29 @@ class PoseStream:
     dies at the next hop by the carry's own score test. Landmark accuracy on real imagery and the effect
     of the gate on pose accuracy are unmeasured. With landmarks=False nothing changes.
 
+    pnp=True (needs landmarks=True and pnp_huber_px, a Huber threshold in pixels that nothing here derives)
+    poses every frame of the window against the landmark map (LandmarkMap.pnp, DESIGN.md "PnP refinement"):
+    one comet_landmark_pnp launch per hop, after the landmark launch, runs pnp_iters Gauss-Newton steps from
+    the fused pose (4: a stated number of steps, not a tuned value). Results then carry pnp_R [T, 4], pnp_T
+    [T, 3] float64, pnp_inliers, pnp_rms_px and pnp_state (1 solved; else the pose is the fused one);
+    fewer than pnp_min_pts usable landmarks leave a frame unsolved. pnp_weight = 0 reports only;
+    pnp_weight > 0 adds the solved poses of the positions [stride, T) to the fusion accumulator as one
+    hypothesis of that weight each, which the next hop's fused poses then include. On a synthetic
+    trajectory that feedback lowers the (u, v, z) drift and raises the rotation drift; accuracy on real
+    imagery is unmeasured and no value of these keywords is recommended. With pnp=False nothing changes.
+
     One stream (batch 1). The model is used as is (its eval / train mode included)."""
 
     def __init__(self, model, window, stride=1, capacity=None, query_fn=None, anchor=None, precision=None,
                  fuse=False, fuse_weight=None, carry=False, carry_tracks=512, carry_cell=8, carry_border=0,
                  carry_min_score=None, detect_every=1, candidate_fn=None, mask_fn=None, warm=False, warm_mode="hold",
                  warm_iters=None, landmarks=False, track_intr=None, lm_min_obs=3, lm_min_pivot=1e-8, lm_weight=None,
-                 lm_gate_px=None, lm_inverse_rotation=0):
+                 lm_gate_px=None, lm_inverse_rotation=0, pnp=False, pnp_iters=4, pnp_huber_px=None, pnp_min_pts=6,
+                 pnp_weight=0.0):
         self.model = model
         _check_landmarks(landmarks, fuse, carry, None if track_intr is None else [track_intr], 1, lm_weight, lm_gate_px)
+        self._pnp = _check_pnp(pnp, landmarks, pnp_iters, pnp_huber_px, pnp_min_pts, pnp_weight)
+        self.pnp = self._pnp is not None
         self.landmarks, self.lm_weight = bool(landmarks), lm_weight
         self.lm_gate_px = None if lm_gate_px is None else float(lm_gate_px)
         self._lm = None
@@ -929,9 +1010,12 @@ class PoseStream:
             fo = self._fuser.fuse(enc, [(0, hop)], w)
             res = res._replace(**_fused_fields(fo, 0, self._fuser.sched.final))
             if self.landmarks:  # (after the fuse launch: the landmarks read this push's fused poses)
-                lo, sc = _landmark_step(self._lm, [0], tr, sc, fo, co.ids, co.src, self.lm_weight, self.lm_gate_px)
+                lo, sc, po = _landmark_step(self._lm, [0], tr, sc, fo, co.ids, co.src, self.lm_weight, self.lm_gate_px,
+                                            self._pnp, self._fuser, [(0, hop)])
                 self._carry.update([0], tr, sc)
                 res = res.with_landmarks(lo, 0)
+                if po is not None:
+                    res = res.with_pnp(po, 0)
             return res
         if self.anchor is not None:
             R, Tx = self._decode(enc, T)
@@ -1085,7 +1169,8 @@ class StreamPool:
     then later hops); otherwise the hops due stay one group. The result order is unchanged.
     landmarks / track_intrs (one (fx, fy, cx, cy) per stream) / lm_*: as PoseStream's; one
     comet_landmark_update launch, after the fuse launch, serves all the hops due in a push (the rows of two
-    warm-start calls are stacked first); reset(stream) forgets that stream's landmarks.
+    warm-start calls are stacked first); reset(stream) forgets that stream's landmarks. pnp / pnp_*: as
+    PoseStream's; one comet_landmark_pnp launch per push, on the rows of the landmark launch in its order.
 
     push() -> [(stream id, StreamResult)] ordered by stream id. The tensors of a result are views
     of the batched outputs. The model is used as is (its eval / train mode included)."""
@@ -1096,10 +1181,13 @@ class StreamPool:
                  fuse=False, fuse_weight=None, carry=False, carry_tracks=512, carry_cell=8, carry_border=0,
                  carry_min_score=None, detect_every=1, candidate_fn=None, mask_fn=None, warm=False, warm_mode="hold",
                  warm_iters=None, landmarks=False, track_intrs=None, lm_min_obs=3, lm_min_pivot=1e-8, lm_weight=None,
-                 lm_gate_px=None, lm_inverse_rotation=0):
+                 lm_gate_px=None, lm_inverse_rotation=0, pnp=False, pnp_iters=4, pnp_huber_px=None, pnp_min_pts=6,
+                 pnp_weight=0.0):
         self.model = model
         self.sched = PoolSchedule(streams, window, stride, capacity)
         _check_landmarks(landmarks, fuse, carry, track_intrs, self.sched.streams, lm_weight, lm_gate_px)
+        self._pnp = _check_pnp(pnp, landmarks, pnp_iters, pnp_huber_px, pnp_min_pts, pnp_weight)
+        self.pnp = self._pnp is not None
         self.landmarks, self.lm_weight = bool(landmarks), lm_weight
         self.lm_gate_px = None if lm_gate_px is None else float(lm_gate_px)
         self._lm = None
@@ -1312,6 +1400,7 @@ class StreamPool:
             ws = [_score_weights(sc) for _, sc in fused]
             w = ws[0] if len(ws) == 1 else torch.cat(ws)
         out = self._fused = self._fuser.fuse(enc, hops, w)
+        self._fused_hops = list(hops)  # (the rows of `out`, for the PnP feedback of _landmarks)
         final = self._fuser.sched.final
         return [(sid, r._replace(**_fused_fields(out, b, final))) for b, (sid, r) in enumerate(results)]
 
@@ -1326,9 +1415,13 @@ class StreamPool:
             rows = self._table(order)[0].long()
             ids, src = ids.index_select(0, rows), src.index_select(0, rows)
         sids = [sid for sid, _ in results]
-        lo, sc = _landmark_step(self._lm, sids, tr, sc, self._fused, ids, src, self.lm_weight, self.lm_gate_px)
+        lo, sc, po = _landmark_step(self._lm, sids, tr, sc, self._fused, ids, src, self.lm_weight, self.lm_gate_px,
+                                    self._pnp, self._fuser, self._fused_hops)
         self._carry.update(sids, tr, sc)
-        return [(sid, r.with_landmarks(lo, b)) for b, (sid, r) in enumerate(results)]
+        results = [(sid, r.with_landmarks(lo, b)) for b, (sid, r) in enumerate(results)]
+        if po is not None:
+            results = [(sid, r.with_pnp(po, b)) for b, (sid, r) in enumerate(results)]
+        return results
 
     @torch.no_grad()
     def push(self, frames, streams=None, query_points=None):

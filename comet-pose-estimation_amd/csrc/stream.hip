@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "fuse_row.hpp"
 
 namespace comet {
 namespace {
@@ -106,7 +107,6 @@ __global__ __launch_bounds__(RING_THREADS) void ring_scatter_kernel(RingArgs a) 
 
 // ---- pose fusion --------------------------------------------------------------------------------
 constexpr int FUSE_THREADS = 64;
-constexpr int FUSE_ROW = COMET_FUSE_ROW;  // doubles per accumulator row
 constexpr int FUSE_SWEEPS = 8;            // cyclic Jacobi sweeps of the 4 x 4 problem
 
 // Everything from here to the end of the file is plain IEEE double evaluated as written (no
@@ -199,40 +199,6 @@ __device__ __forceinline__ FusedPose fuse_row(const double (&r)[FUSE_ROW]) {
 #pragma unroll
   for (int k = 0; k < 3; ++k) f.uvz[k] = r[11 + k] / f.W;
   return f;
-}
-
-__device__ __forceinline__ void load_row(const double* p, double (&r)[FUSE_ROW]) {
-#pragma unroll
-  for (int k = 0; k < FUSE_ROW; k += 2) {
-    const double2 d = *reinterpret_cast<const double2*>(p + k);
-    r[k] = d.x;
-    r[k + 1] = d.y;
-  }
-}
-__device__ __forceinline__ void store_row(double* p, const double (&r)[FUSE_ROW]) {
-#pragma unroll
-  for (int k = 0; k < FUSE_ROW; k += 2) *reinterpret_cast<double2*>(p + k) = double2{r[k], r[k + 1]};
-}
-
-// row += one hypothesis (unit q, (u, v, z)) of weight w
-__device__ __forceinline__ void add_hypothesis(double (&r)[FUSE_ROW], double w, const double (&q)[4],
-                                               const double (&x)[3]) {
-  double h[FUSE_ROW];
-  h[0] = w;
-  int k = 1;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = i; j < 4; ++j) h[k++] = w * (q[i] * q[j]);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    h[11 + i] = w * x[i];
-    h[14 + i] = w * (x[i] * x[i]);
-  }
-  h[17] = 1.0;
-  h[18] = h[19] = 0.0;
-#pragma unroll
-  for (int i = 0; i < FUSE_ROW; ++i) r[i] += h[i];
 }
 
 __device__ __forceinline__ void zero_row(double (&r)[FUSE_ROW]) {

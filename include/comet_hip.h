@@ -714,6 +714,66 @@ int comet_landmark_update(const float* tracks, const float* weights, const float
                           int inverse_rotation, int min_obs, double min_pivot, double* X, int32_t* n_obs,
                           float* err_px, int32_t* state, void* stream);
 
+/* comet_landmark_pnp (DESIGN.md "PnP refinement"): the landmarks are 3-D points in the body frame and the
+ *   window's tracks their 2-D observations, so every frame of a window has a perspective-n-point problem.
+ *   This solves it for every (hop h, window position i) of a push by `iters` Gauss-Newton steps with a
+ *   Huber weight, starting from the fused pose, in one launch after that push's comet_pose_fuse and
+ *   comet_landmark_update launches: grid (T, n), one workgroup of 256 threads per (i, h), no atomics, no
+ *   communication between workgroups. Everything is IEEE double evaluated as written (no contraction), and
+ *   only + - * / and sqrt.
+ *   Inputs: tracks [n, T, N, 2] f32 pixels; weights [n, T, N] f32 or NULL (= 1); X [n, N, 3] f64 and
+ *     state [n, N] int32 as comet_landmark_update wrote them in this push; R0 [n, T, 4] f32 (w first) and
+ *     T0 [n, T, 3] f64, the fused pose, the starting point; intr [n, 4] f64 = (fx, fy, cx, cy) of the pixels
+ *     the tracks live in, intr_host the same values on the host.
+ *   Pose: Rm = the matrix of R0[h, i] by the formula of comet_landmark_update (its transpose when
+ *     inverse_rotation = 1), t = T0[h, i], q = R0[h, i] widened to double. Not all finite: state -1.
+ *   Usable point j at a pose: state[h, j] == 1; x, y and w finite; w > 0; Xc = Rm X + t has Xc.z > 0.
+ *   Residual r = (fx (Xc.x / Xc.z) + cx - x, fy (Xc.y / Xc.z) + cy - y), |r| = sqrt(r0^2 + r1^2); Huber
+ *     weight wh = 1 if |r| <= huber_px else huber_px / |r|. Perturbation on the left, in the camera frame:
+ *     Xc' = Xc + omega x Xc + upsilon, J = Jproj [ -[Xc]x | I ] (2 x 6); with a0 = fx / z, a1 = fy / z,
+ *     c0 = a0 (x / z), c1 = a1 (y / z) its rows are
+ *       J0 = (-(c0 y), a0 z + c0 x, -(a0 y), a0, 0, -c0),  J1 = (-(a1 z) - c1 y, c1 x, a1 x, 0, a1, -c1).
+ *   Per iteration: a point adds (w wh) (J0_r J0_c + J1_r J1_c) to the upper triangle of H (21 values, row
+ *     by row), (w wh) (J0_r r0 + J1_r r1) to b (6 values) and 1 to the usable count. Thread t sums its
+ *     slots j = t, t + 256, ... in ascending order from +0; the 256 partials are combined by the fixed
+ *     tree p[t] += p[t + d], d = 128, 64, ..., 1 (LDS for d >= 64, wave shuffles below).
+ *     A count below min_pts: state 0. A sum that is not finite: state -1.
+ *   Solve H delta = -b by an unpivoted LDL^T: column j: c_i = H_ij - sum_{k < j} L_jk U_ik (k ascending),
+ *     d_j = c_j, U_ij = c_i, L_ij = c_i / d_j; y_i = -b_i - sum_{k < i} L_ik y_k; delta_i = y_i / d_i -
+ *     sum_{k > i} L_ki delta_k (k ascending). A pivot d_j <= min_pivot * max(diag H): state 2.
+ *   Update with delta = (omega, upsilon): dq = (1, omega / 2) / sqrt(1 + |omega / 2|^2); Rm <- R(dq) Rm;
+ *     t <- R(dq) t + upsilon; q <- dq (x) q (inverse_rotation = 0) or q (x) conj(dq) (1), divided by its
+ *     norm with w >= 0. A value of the new pose that is not finite: state -1.
+ *   Final pass at the last pose: n_in = usable points with |r| <= huber_px; rms_px = sqrt(sum w (r0^2 +
+ *     r1^2) / sum w) over the usable points, summed by the same tree. A usable count below min_pts here:
+ *     state 0; rms_px not finite: state -1.
+ *   Outputs per (h, i): q [4] f64 (unit, w >= 0), R [4] f32 (q rounded), t [3] f64, n_in int32, rms_px f32,
+ *     state int32: 1 solved | 0 fewer than min_pts usable points | 2 degenerate pivot | -1 not finite. For
+ *     every state other than 1: R = R0 and t = T0 bit for bit, q = R0 widened, n_in = 0, rms_px = +inf.
+ *   Injection (optional): fuse_acc [rows, COMET_FUSE_ROW] f64, the accumulator of comet_pose_fuse, or NULL;
+ *     slots [n * T] int32 / slots_host, the tables of that push's comet_pose_fuse call (read only with
+ *     fuse_acc); inject_w; (fuse_fx, fuse_fy, fuse_cx, fuse_cy) the fuser's intrinsics. With fuse_acc and
+ *     inject_w > 0, thread 0 of a position i in [s, T) with state 1 adds one hypothesis of weight inject_w
+ *     to row slots[h * T + i], as comet_pose_fuse adds one: q as returned, (u, v, z) = (cx + fx tx / tz,
+ *     cy + fy ty / tz, tz) left to right, every sum of the row layout, count + 1. Nothing is added when
+ *     (u, v, z) is not finite. Positions [0, s) are final and never touched; nothing else is written.
+ *   COMET_EINVAL before anything is launched, checked in this order: a null pointer (weights may be null;
+ *   fuse_acc may be null, and then slots and slots_host may be too), n < 1, N outside [1, 4096], T < 2,
+ *   s outside [1, T - 1], iters outside [1, COMET_PNP_MAX_ITERS], huber_px not finite and positive,
+ *   min_pts < 4, min_pivot outside [0, 1), inverse_rotation not 0 or 1, host intrinsics whose fx or fy is
+ *   not finite and positive; with fuse_acc: inject_w not finite or negative, a host slot outside [0, rows),
+ *   two equal host slots; then tracks / X / T0 / intr / q / t not 8-B aligned or R0 / fuse_acc not 16-B
+ *   aligned. The kernel range-checks every index before it addresses memory.
+ *   LDS: 42 KiB of partial sums + 100 B, static. */
+#define COMET_PNP_MAX_ITERS 16
+int comet_landmark_pnp(const float* tracks, const float* weights, const double* X, const int32_t* state,
+                       const float* R0, const double* T0, const double* intr, const double* intr_host, int n,
+                       int Tw, int N, int s, int inverse_rotation, int iters, double huber_px, int min_pts,
+                       double min_pivot, double* fuse_acc, int rows, const int32_t* slots,
+                       const int32_t* slots_host, double inject_w, double fuse_fx, double fuse_fy, double fuse_cx,
+                       double fuse_cy, double* q_out, float* R_out, double* t_out, int32_t* n_in, float* rms_px,
+                       int32_t* state_out, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Debug support (bounds asserts and a NaN / Inf check mode).
  * comet_count_nonfinite: adds the number of NaN / Inf elements of x (n elements, dtype) to

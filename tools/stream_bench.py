@@ -53,7 +53,12 @@ weights, which converge to nothing meaningful, so it is not an accuracy figure.
 --fuse --carry --landmarks: the landmark map (comet_landmark_update, DESIGN.md "Landmarks"): two
 PoseStream(fuse=True, carry=True) objects, landmarks on and off, alternate push by push in one process;
 ms per push of each, the comet_landmark_update launch of a hop alone (20 back-to-back launches / 20), the
-valid landmarks per hop and whether pred_pose_enc stayed identical. A report, not a pass criterion."""
+valid landmarks per hop and whether pred_pose_enc stayed identical. A report, not a pass criterion.
+--fuse --carry --landmarks --pnp: the PnP refinement (comet_landmark_pnp, DESIGN.md "PnP refinement"): two
+PoseStream(fuse=True, carry=True, landmarks=True) objects, pnp on (report only, pnp_weight 0) and off,
+alternate push by push in one process; ms per push of each, the comet_landmark_pnp launch of a hop alone
+(20 back-to-back launches / 20), the solved positions per hop and whether pred_pose_enc stayed identical.
+A report, not a pass criterion."""
 import argparse
 import json
 import os
@@ -333,6 +338,62 @@ def landmark_bench(model, args, dev, cfg):
         flush=True)
 
 
+def pnp_bench(model, args, dev, cfg):
+    """--pnp (with --fuse --carry --landmarks): ms per push of PoseStream(fuse, carry, landmarks) with pnp on
+    (report only) against off, the two objects alternating push by push in one process, and the
+    comet_landmark_pnp launch alone on the hop's own outputs."""
+    from comet_amd import loop
+    from comet_amd.data import crop_intrinsics
+    from comet_amd.models.utils import INTRINSICS
+    from comet_amd.ops import LandmarkOut
+    from comet_amd.stream import LandmarkMap, PoseStream, keypoint_candidates
+    T, S, N = args.frames, args.image, args.tracks
+    g = torch.Generator(device=dev).manual_seed(1)
+    total = T + args.warmup + args.hops - 1
+    frames = torch.randn(total, 3, S, S, device=dev, generator=g)
+    sp = loop._keypoint_init(cfg, dev)
+    R0 = torch.tensor([0.8, 0.2, -0.4, 0.4], device=dev)
+    anchor = (R0 / R0.norm(), torch.tensor([331.25, 247.5, 11.375], device=dev), 268.44, 0.5, "AMD")
+    intr = crop_intrinsics(INTRINSICS["AMD"], (0, 0, 2 * S, 2 * S), S)
+    kw = dict(window=T, stride=1, precision=torch.bfloat16, anchor=anchor, fuse=True, carry=True, carry_tracks=N,
+              carry_cell=args.cell, carry_min_score=args.min_score, candidate_fn=keypoint_candidates(sp),
+              landmarks=True, track_intr=intr)
+    objs = {True: PoseStream(model, pnp=True, pnp_huber_px=args.pnp_huber_px, **kw), False: PoseStream(model, **kw)}
+    scratch = LandmarkMap(T, 1, 1, N, [intr])
+    for o in objs.values():
+        assert o.push(frames[:T - 1]) == []
+    ta, tb, tc, solved, same = [], [], [], [], True
+    for j in range(args.warmup + args.hops):
+        i = j + T - 1
+        order = (True, False) if j % 2 == 0 else (False, True)  # (neither path always runs first)
+        ms, res = {}, {}
+        for f in order:
+            ms[f], res[f] = _timed(lambda: objs[f].push(frames[i]))
+        r = res[True][0]
+        tr, fr, ft = r.pred_tracks.float()[None].contiguous(), r.fused_R[None].contiguous(), r.fused_T[None].contiguous()
+        lo = LandmarkOut(r.landmarks[None].contiguous(), r.landmark_obs[None].contiguous(),
+                         r.landmark_err[None].contiguous(), r.landmark_state[None].contiguous())
+        ms_c, _ = _timed(lambda: [scratch.pnp([0], tr, fr, ft, lo, huber_px=args.pnp_huber_px) for _ in range(GATHER_REPS)])
+        if j >= args.warmup:
+            ta.append(ms[True])
+            tb.append(ms[False])
+            tc.append(ms_c / GATHER_REPS)
+            solved.append(int((r.pnp_state == 1).sum()))
+            same = same and torch.equal(r.pred_pose_enc, res[False][0].pred_pose_enc)
+    a, b, c = statistics.median(ta), statistics.median(tb), statistics.median(tc)
+    print(json.dumps({
+        "metric": f"ms per push, pnp on against off, PoseStream fuse + carry + landmarks, T={T} {S}^2 N={N}, bf16, stride 1",
+        "pnp_on_ms": round(a, 3), "pnp_off_ms": round(b, 3), "on_over_off": round(a / b, 4),
+        "min_pnp_on_ms": round(min(ta), 3), "min_pnp_off_ms": round(min(tb), 3),
+        "landmark_pnp_ms": round(c, 4), "min_landmark_pnp_ms": round(min(tc), 4),
+        "landmark_pnp_timing": f"device events around {GATHER_REPS} back-to-back launches / {GATHER_REPS}, median over the pushes",
+        "pnp_iters": 4, "pnp_huber_px": args.pnp_huber_px,
+        "solved_positions_per_hop": {"mean": round(statistics.mean(solved), 2), "min": min(solved), "max": max(solved)},
+        "pred_pose_enc_identical_on_vs_off": same, "pushes": args.hops, "warmup": args.warmup,
+        "data": "synthetic (N(0,1) frames, detector candidates); random-init weights: the poses carry no geometry"}),
+        flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16, help="window length T")
@@ -354,6 +415,9 @@ def main():
     ap.add_argument("--warm-mode", type=str, default="hold", choices=("hold", "velocity"), help="--warm: warm_mode")
     ap.add_argument("--landmarks", action="store_true",
                     help="--fuse --carry: time the landmark map (comet_landmark_update) on against off")
+    ap.add_argument("--pnp", action="store_true",
+                    help="--fuse --carry --landmarks: time the PnP refinement (comet_landmark_pnp) on against off")
+    ap.add_argument("--pnp-huber-px", type=float, default=3.0, help="--pnp: pnp_huber_px (not a recommendation)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         print("stream_bench: no GPU", file=sys.stderr)
@@ -371,8 +435,13 @@ def main():
     if args.landmarks:
         if not (args.fuse and args.carry):
             ap.error("--landmarks needs --fuse --carry")
+        if args.pnp:
+            pnp_bench(model, args, dev, cfg)
+            return 0
         landmark_bench(model, args, dev, cfg)
         return 0
+    if args.pnp:
+        ap.error("--pnp needs --fuse --carry --landmarks")
     if args.carry:
         carry_bench(model, args, dev, cfg)
         return 0
