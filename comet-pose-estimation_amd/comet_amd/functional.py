@@ -343,6 +343,7 @@ class _LayerNormDual(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, eps):
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as zeros
         y, y16, mean, rstd = ops.layernorm(x, None, None, eps=eps, out_dtype=torch.float32, stats=True, dual=True)
         ctx.save_for_backward(x, mean, rstd)
         return y, y16
@@ -365,6 +366,7 @@ class _ResLayerNorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, eps):
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as zeros
         y, mean, rstd = ops.layernorm(x, eps=eps, out_dtype=compute_dtype(), stats=True)
         ctx.save_for_backward(x, mean, rstd)
         return x.view_as(x), y
@@ -396,6 +398,7 @@ class _LinearPair(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xq, xkv, w, b, C):
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as zeros
         ctx.cdt = compute_dtype()
         wc = wcast(w, ctx.cdt)
         xq2 = xq.reshape(-1, xq.shape[-1])
@@ -472,6 +475,7 @@ class _FrameSplit(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tok):
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as zeros
         ctx.shape, ctx.dtype = tok.shape, tok.dtype
         # frames 1.. as one contiguous copy: the consumers (LayerNorm forward and backward of the
         # cross-attention block) would each make it contiguous otherwise

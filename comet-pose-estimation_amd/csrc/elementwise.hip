@@ -456,8 +456,11 @@ extern "C" int comet_adamw_multi(float* const* params, const float* const* grads
                                  const float* sqnorm, float max_norm, void* stream) {
   COMET_CHECK_ARG(step >= 1, "comet_adamw_multi: step must be >= 1");
   hipStream_t s = as_stream(stream);
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
+  // bias corrections in double, as torch computes them on the host: 1 - powf(beta2, step) in f32
+  // cancels (beta2 = 0.999, step 2: half an ulp of 0.998 is 1.5e-5 of the 0.002 left), which moved
+  // the step size of the early steps by up to 7e-6 relative
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+  const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   for (int base = 0; base < n_tensors; base += MT_MAX) {
     MultiPtr mp{};
     mp.count = n_tensors - base < MT_MAX ? n_tensors - base : MT_MAX;
