@@ -9,7 +9,7 @@ them once per frame, keeps their outputs in device rings, and for every hop gath
 (model(..., frame_cache=...)).
 
   RingSchedule   the slot / hop arithmetic, host only (no tensors)
-  PoseStream     push(frame | frames) -> one StreamResult per completed hop
+  PoseStream     push(frame | frames) -> one StreamResult per completed hop; a StreamPool of one stream
   PoolSchedule   the same arithmetic for S streams over pooled rings, host only
   StreamPool     S streams on one model: push(one frame per stream) runs the per-frame stages, the
                  ring store (comet_ring_scatter) and the hops that fall due as one batch each
@@ -786,6 +786,11 @@ class LandmarkMap:
         return ids[b][on], out.X[b][on], out.n_obs[b][on]
 
 
+def _per_frame(cache):
+    """FrameCache of one k-frame sequence -> its tensors as [k, ...] (None where unused)."""
+    return [None if cache.fmaps is None else cache.fmaps[0], cache.refine_frames[0], cache.tokens]
+
+
 class PoseStream:
     """Sliding-window pose estimation over a frame stream.
 
@@ -870,7 +875,10 @@ class PoseStream:
     trajectory that feedback lowers the (u, v, z) drift and raises the rotation drift; accuracy on real
     imagery is unmeasured and no value of these keywords is recommended. With pnp=False nothing changes.
 
-    One stream (batch 1). The model is used as is (its eval / train mode included)."""
+    One stream (batch 1): a PoseStream is a StreamPool of one stream. push() runs the per-frame stages on
+    its k frames as one batch and hands them, frame by frame, to the pool's hop pipeline
+    (StreamPool._advance), which is the only implementation of everything above. The model is used as is
+    (its eval / train mode included)."""
 
     def __init__(self, model, window, stride=1, capacity=None, query_fn=None, anchor=None, precision=None,
                  fuse=False, fuse_weight=None, carry=False, carry_tracks=512, carry_cell=8, carry_border=0,
@@ -878,148 +886,34 @@ class PoseStream:
                  warm_iters=None, landmarks=False, track_intr=None, lm_min_obs=3, lm_min_pivot=1e-8, lm_weight=None,
                  lm_gate_px=None, lm_inverse_rotation=0, pnp=False, pnp_iters=4, pnp_huber_px=None, pnp_min_pts=6,
                  pnp_weight=0.0):
-        self.model = model
-        _check_landmarks(landmarks, fuse, carry, None if track_intr is None else [track_intr], 1, lm_weight, lm_gate_px)
-        self._pnp = _check_pnp(pnp, landmarks, pnp_iters, pnp_huber_px, pnp_min_pts, pnp_weight)
-        self.pnp = self._pnp is not None
-        self.landmarks, self.lm_weight = bool(landmarks), lm_weight
-        self.lm_gate_px = None if lm_gate_px is None else float(lm_gate_px)
-        self._lm = None
-        if self.landmarks:
-            self._lm = LandmarkMap(window, stride, 1, carry_tracks, [track_intr], lm_min_obs, lm_min_pivot,
-                                   lm_inverse_rotation)
-        self.sched = RingSchedule(window, stride, capacity)
-        self.query_fn = query_fn
-        self.carry, self.candidate_fn, self.mask_fn = bool(carry), candidate_fn, mask_fn
-        _check_warm(warm, self.carry, warm_mode, warm_iters)
-        self.warm, self.warm_mode = bool(warm), warm_mode
-        self.warm_iters = None if warm_iters is None else int(warm_iters)
-        self._carry = None
-        if self.carry:
-            self.sched.chain_index()  # raises unless stride < window
-            _check_carry(True, candidate_fn)
-            self._carry = TrackCarry(window, stride, 1, carry_tracks, carry_cell, carry_border, carry_min_score,
-                                     detect_every, warm_mode if self.warm else None)
-        self.precision = precision if precision is not None else _model_precision(model)
-        _check_fuse(fuse, fuse_weight, anchor is not None)
-        self.fuse, self.fuse_weight = bool(fuse), fuse_weight
-        self._fuser = None
-        self.anchor = None
-        if anchor is not None:
-            self.sched.chain_index()  # raises unless stride < window
-            self.anchor = Anchor(*anchor)
-        self.reset()
+        self._pool = StreamPool(
+            model, 1, window, stride, capacity, query_fn, None if anchor is None else [anchor], precision, fuse=fuse,
+            fuse_weight=fuse_weight, carry=carry, carry_tracks=carry_tracks, carry_cell=carry_cell,
+            carry_border=carry_border, carry_min_score=carry_min_score, detect_every=detect_every,
+            candidate_fn=candidate_fn, mask_fn=mask_fn, warm=warm, warm_mode=warm_mode, warm_iters=warm_iters,
+            landmarks=landmarks, track_intrs=None if track_intr is None else [track_intr], lm_min_obs=lm_min_obs,
+            lm_min_pivot=lm_min_pivot, lm_weight=lm_weight, lm_gate_px=lm_gate_px,
+            lm_inverse_rotation=lm_inverse_rotation, pnp=pnp, pnp_iters=pnp_iters, pnp_huber_px=pnp_huber_px,
+            pnp_min_pts=pnp_min_pts, pnp_weight=pnp_weight)
+        self.sched = self._pool.sched.scheds[0]  # the stream's own RingSchedule
+        self.anchor = None if anchor is None else self._pool.anchors[0]
+        self._hw = None  # the frame size push() holds the stream to
+
+    # what a caller reads off a stream is the pool's (landmark_map: the LandmarkMap, or None)
+    _POOLED = frozenset(("model", "query_fn", "precision", "fuse", "fuse_weight", "carry", "candidate_fn", "mask_fn",
+                         "warm", "warm_mode", "warm_iters", "landmarks", "lm_weight", "lm_gate_px", "pnp", "landmark_map",
+                         "_pnp", "_carry", "_lm", "_fuser", "_rings", "_wins"))
+
+    def __getattr__(self, name):
+        if name in self._POOLED:
+            return getattr(self._pool, name)
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     def reset(self):
-        """Forget every frame (the next push starts a new stream at frame 0, at the anchor)."""
-        self.sched.reset()
-        self._rings = None   # FrameCache-ordered list of [capacity, ...] tensors (None where unused)
-        self._wins = None    # the gathered window, same order, [window, ...]
+        """Forget every frame (the next push starts a new stream at frame 0, at the anchor; a new frame
+        size may follow)."""
         self._hw = None
-        self._ref = None     # (R [4] f32, T_uvz [3] f32) the next hop is decoded against
-        if self._fuser is not None:
-            self._fuser.reset()
-        if self._carry is not None:
-            self._carry.reset()
-        if self._lm is not None:
-            self._lm.reset()
-
-    @property
-    def landmark_map(self):
-        """The LandmarkMap (landmarks=True), else None."""
-        return self._lm
-
-    # -- ring -------------------------------------------------------------------------------------
-    @staticmethod
-    def _per_frame(cache):
-        """FrameCache of one k-frame sequence -> its tensors as [k, ...] (None where unused)."""
-        return [None if cache.fmaps is None else cache.fmaps[0], cache.refine_frames[0], cache.tokens]
-
-    def _allocate(self, per, dev):
-        cap, T = self.sched.capacity, self.sched.window
-        self._rings, self._wins = [], []
-        for t in per:
-            if t is None:
-                self._rings.append(None)
-                self._wins.append(None)
-                continue
-            slot = t.shape[1:]
-            if (slot.numel() * t.element_size()) % 16 != 0:
-                raise ValueError(f"frame size not supported by the ring: a slot of {tuple(slot)} {t.dtype} is no "
-                                 "multiple of 16 bytes")
-            self._rings.append(torch.empty(cap, *slot, device=dev, dtype=t.dtype))
-            self._wins.append(torch.empty(T, *slot, device=dev, dtype=t.dtype))
-        # the slot table of every possible head, on the device and on the host
-        rows = [self.sched.window_slots(h) for h in range(cap)]
-        self._tables = torch.tensor(rows, dtype=torch.int32, device=dev)
-        self._tables_host = [(ctypes.c_int32 * T)(*r) for r in rows]
-
-    def _store(self, per, i, slot):
-        for ring, t in zip(self._rings, per):
-            if ring is not None:
-                ring[slot].copy_(t[i])
-
-    def _gather(self, head):
-        """The window whose first frame sits in slot `head`, contiguous, as a FrameCache (B = 1)."""
-        pairs = [(r, w) for r, w in zip(self._rings, self._wins) if r is not None]
-        ops.ring_gather(pairs, self._tables[head], self._tables_host[head])
-        from .models.E2Epose2 import FrameCache
-        fm, fr, tok = self._wins
-        return FrameCache(fmaps=None if fm is None else fm[None], refine_frames=fr[None], tokens=tok)
-
-    # -- hops -------------------------------------------------------------------------------------
-    def _decode(self, enc, T):
-        R, Tx, self._ref = _decode_chained(self.anchor, self._ref, self._ratio, self.sched.chain_index(), enc, T)
-        return R, Tx
-
-    def _hop(self, hop, query_points):
-        T = self.sched.window
-        cache = self._gather(hop.head)
-        co = wo = None
-        extra = {}
-        if self.carry:
-            frame = cache.refine_frames[0, 0]
-            cand = self.candidate_fn(frame) if self._carry.detects(0) else None
-            mask = self.mask_fn(frame) if self.mask_fn is not None else None
-            first = self._carry.sched.is_first(0)
-            if self.warm:
-                self._carry.warm_div = _warm_div(self.model)
-            co = self._carry.step([0], frame.shape[-2], frame.shape[-1], [cand], [mask])
-            query_points = co.query[0]
-            if self.warm:
-                wo = self._carry.warm
-                if not first:  # (a first hop is cold and runs the config's iterations: the call as it always was)
-                    extra = dict(track_init=wo.coords, track_iters=self.warm_iters)
-        elif query_points is None:
-            query_points = self.query_fn(cache.refine_frames[0, 0])
-        q = query_points.to(self._tables.device, torch.float32)
-        tracks = q[None, None].expand(1, T, -1, 2)
-        # (with a frame_cache the model reads only the shape of its image argument)
-        out = self.model(cache.refine_frames, training=False, tracks=tracks, frame_cache=cache, **extra)
-        enc = out["pred_pose_enc"]
-        tr = out.get("pred_tracks")
-        sc = out.get("_track_predictions", {}).get("pred_score")
-        R = Tx = None
-        res = StreamResult(hop.frame_index, enc, None if tr is None else tr[0], None if sc is None else sc[0])
-        if co is not None:
-            if not self.landmarks:
-                self._carry.update([0], tr, sc)
-            res = res.with_tracks(*_carry_fields(co, 0, wo))
-        if self.fuse:
-            w = _score_weights(sc) if self.fuse_weight == "score" else None
-            fo = self._fuser.fuse(enc, [(0, hop)], w)
-            res = res._replace(**_fused_fields(fo, 0, self._fuser.sched.final))
-            if self.landmarks:  # (after the fuse launch: the landmarks read this push's fused poses)
-                lo, sc, po = _landmark_step(self._lm, [0], tr, sc, fo, co.ids, co.src, self.lm_weight, self.lm_gate_px,
-                                            self._pnp, self._fuser, [(0, hop)])
-                self._carry.update([0], tr, sc)
-                res = res.with_landmarks(lo, 0)
-                if po is not None:
-                    res = res.with_pnp(po, 0)
-            return res
-        if self.anchor is not None:
-            R, Tx = self._decode(enc, T)
-        return res._replace(R=R, T=Tx)
+        self._pool.reset()
 
     @torch.no_grad()
     def push(self, frames, query_points=None):
@@ -1032,28 +926,17 @@ class PoseStream:
         hw = tuple(frames.shape[-2:])
         if self._hw is not None and hw != self._hw:
             raise ValueError(f"frame size changed from {self._hw} to {hw}; reset() starts a new stream")
-        _check_carry(self.carry, self.candidate_fn, query_points)
-        if query_points is None and self.query_fn is None and not self.carry:
+        pool = self._pool
+        _check_carry(pool.carry, pool.candidate_fn, query_points)
+        if query_points is None and pool.query_fn is None and not pool.carry:
             raise ValueError("no query source: pass query_points to push() or query_fn to PoseStream")
         results = []
-        with F.precision(self.precision):
-            per = self._per_frame(self.model.frame_stages(frames.float()))
-            if self._rings is None:
-                self._allocate(per, frames.device)
-                self._hw = hw
-                if self.fuse:
-                    if self._fuser is None or self._fuser.device != frames.device:
-                        from .models.utils import INTRINSICS
-                        a = self.anchor
-                        self._fuser = PoseFuser(self.sched.window, self.sched.stride, self.sched.capacity, 1,
-                                                [(a.R, a.T_uvz)], a.ratio, INTRINSICS[a.dataset], frames.device)
-                elif self.anchor is not None:
-                    self._ref, self._ratio = _anchor_ref(self.anchor, frames.device)
-            for i in range(frames.shape[0]):
-                slot, hop = self.sched.push()
-                self._store(per, i, slot)
-                if hop is not None:
-                    results.append(self._hop(hop, query_points))
+        with F.precision(pool.precision):
+            per = _per_frame(pool.model.frame_stages(frames.float()))  # one batched call for the k frames
+            self._hw = hw
+            for i in range(frames.shape[0]):  # (frame i's hop is complete before frame i + 1 is stored)
+                rows = [None if t is None else t[i:i + 1] for t in per]
+                results += [r for _, r in pool._advance(rows, [0], query_points)]
         return results
 
 
@@ -1137,7 +1020,8 @@ class PoolSchedule:
 
 
 class StreamPool:
-    """Several PoseStream-like streams that share one model and batch their work.
+    """Several streams that share one model and batch their work: the hop pipeline of this module
+    (PoseStream is a pool of one stream; its docstring describes every keyword).
 
         pool = StreamPool(model, streams=S, window=16, query_fn=keypoint_query(sp))
         for frames in cameras:                       # [S, 3, H, W], one new frame per stream
@@ -1156,9 +1040,9 @@ class StreamPool:
     by stream id), else query_fn(first frame of the window). Hops whose query counts differ
     (filter_and_pad returns between min_required and track_num points) are grouped by N, one
     batched call per group. anchors: a dict or list giving every stream the 5-tuple PoseStream
-    takes; each stream chains its absolute poses as PoseStream does (decoded per stream by the same
-    code, so for the same pred_pose_enc the same bits). fuse / fuse_weight: as PoseStream's; all the
-    hops due in a push, of every query-count group, are fused by one comet_pose_fuse launch. With
+    takes; each stream chains its absolute poses on its own (_decode_chained, per stream). fuse /
+    fuse_weight: as PoseStream's; all the hops due in a push, of every query-count group, are fused
+    by one comet_pose_fuse launch. With
     fuse=True every anchor must carry the same ratio and dataset (one launch takes one ratio and one
     set of intrinsics). carry / carry_* / detect_every / candidate_fn / mask_fn: as PoseStream's; every
     carried hop has carry_tracks queries, so the hops due in a push are one group, and one
@@ -1272,8 +1156,9 @@ class StreamPool:
         return self._lm
 
     # -- rings ------------------------------------------------------------------------------------
-    def _allocate(self, per, dev):
+    def _allocate(self, per):
         S, cap, T = self.sched.streams, self.sched.capacity, self.sched.window
+        dev, self._hw = per[1].device, tuple(per[1].shape[-2:])  # (refine_frames: the frames themselves)
         self._rings, self._wins = [], []
         for t in per:
             if t is None:
@@ -1443,35 +1328,41 @@ class StreamPool:
                 missing = [s for s in self.sched.due(ids) if query_points.get(s) is None]
                 if missing:
                     raise ValueError(f"no query source for the streams {missing}, whose hop is due in this push")
-        results = []
         with F.precision(self.precision):
-            per = PoseStream._per_frame(self.model.frame_stages(frames.float()))
-            if self._rings is None:
-                self._allocate(per, frames.device)
-                self._hw = hw
-            slots, hops = self.sched.push(ids)
-            slot_table, slot_host = self._table(slots)
-            ops.ring_scatter([(t.contiguous(), r) for t, r in zip(per, self._rings) if r is not None],
-                             slot_table, slot_host)
-            if hops:
-                fused, order = ([] if self.fuse else None), []
-                later = [] if self.landmarks else None
-                if self.carry:  # every hop has carry_tracks queries: one group, unless the coarse iterations differ
-                    firsts = [self._carry.sched.is_first(sid) for sid, _ in hops]
-                    co = self._carried(hops)
-                    wo = self._carry.warm if self.warm else None
-                    for pos, warm, iters in self._warm_groups(firsts):
-                        results += self._hops(hops, None, pos, fused, co, wo, warm, iters, later)
-                        order += pos
-                else:
-                    qs = [self._query(sid, hop, query_points) for sid, hop in hops]
-                    for _, pos in self.sched.group([q.shape[0] for q in qs]):
-                        results += self._hops(hops, qs, pos, fused)
-                        order += pos
-                if self.fuse:
-                    results = self._fuse([hops[i] for i in order], results, fused)
-                if self.landmarks:
-                    results = self._landmarks(order, results, co, later)
+            return self._advance(_per_frame(self.model.frame_stages(frames.float())), ids, query_points)
+
+    def _advance(self, per, ids, query_points):
+        """The part of a push behind the per-frame stages, called under F.precision and no_grad: per, the
+        FrameCache-ordered tensors with one row per stream of `ids` (_per_frame), go into the rings and
+        the hops that fall due run -> [(stream id, StreamResult)] ordered by stream id. Everything a
+        hop leaves behind (carried tracks, accumulator rows, the chained reference) is in place when
+        this returns, so the stream's next frame may be stored."""
+        if self._rings is None:
+            self._allocate(per)
+        results = []
+        slots, hops = self.sched.push(ids)
+        slot_table, slot_host = self._table(slots)
+        ops.ring_scatter([(t.contiguous(), r) for t, r in zip(per, self._rings) if r is not None],
+                         slot_table, slot_host)
+        if hops:
+            fused, order = ([] if self.fuse else None), []
+            later = [] if self.landmarks else None
+            if self.carry:  # every hop has carry_tracks queries: one group, unless the coarse iterations differ
+                firsts = [self._carry.sched.is_first(sid) for sid, _ in hops]
+                co = self._carried(hops)
+                wo = self._carry.warm if self.warm else None
+                for pos, warm, iters in self._warm_groups(firsts):
+                    results += self._hops(hops, None, pos, fused, co, wo, warm, iters, later)
+                    order += pos
+            else:
+                qs = [self._query(sid, hop, query_points) for sid, hop in hops]
+                for _, pos in self.sched.group([q.shape[0] for q in qs]):
+                    results += self._hops(hops, qs, pos, fused)
+                    order += pos
+            if self.fuse:
+                results = self._fuse([hops[i] for i in order], results, fused)
+            if self.landmarks:
+                results = self._landmarks(order, results, co, later)
         return sorted(results, key=lambda r: r[0])
 
 

@@ -311,3 +311,55 @@ def test_stream_eval_writes_one_row_per_hop(model, data, closed, tmp_path):
     for r in rows:
         quat = torch.tensor([float(r[k]) for k in ("qw", "qx", "qy", "qz")])
         assert abs(float(quat.norm()) - 1) < 1e-3 and float(r["hop_ms"]) > 0
+
+
+# ------------------------------------------------------------------------------------------------
+# several hops inside one push
+# ------------------------------------------------------------------------------------------------
+class _FrameWise:
+    """The model with frame_stages run one frame at a time and concatenated: what the rings hold then
+    does not depend on how the frames were chunked into pushes."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def __getattr__(self, name):
+        return getattr(self.model, name)
+
+    def frame_stages(self, frames):
+        from comet_amd.models.E2Epose2 import FrameCache
+        cs = [self.model.frame_stages(frames[i:i + 1]) for i in range(frames.shape[0])]
+        return FrameCache(fmaps=torch.cat([c.fmaps for c in cs], 1), refine_frames=torch.cat([c.refine_frames for c in cs], 1),
+                          tokens=torch.cat([c.tokens for c in cs]))
+
+
+def test_hops_inside_one_push_leave_their_state_to_the_next(model, data):
+    """fuse + carry + warm + landmarks + pnp with feedback, stride 1, T + 5 frames pushed one at a time and
+    in chunks of 3 (up to three hops complete inside one push): hop i is finished -- carried tracks, fused
+    rows, landmark rows, the PnP poses fed back -- before frame i + 1 is stored, so every field of every
+    result is the same bits."""
+    from comet_amd.stream import StreamResult
+    frames, _ = data
+    cand = (torch.rand(96, 2, generator=torch.Generator().manual_seed(7)) * (HW - 1)).cuda()
+    R0 = torch.tensor([0.8, 0.2, -0.4, 0.4], device="cuda")
+    anchor = (R0 / R0.norm(), torch.tensor([331.25, 247.5, 11.375], device="cuda"), 268.44,
+              torch.tensor([0.5], dtype=torch.float64), "AMD")
+
+    def run(k):
+        s = _stream(_FrameWise(model), torch.float32, stride=1, anchor=anchor, fuse=True, carry=True, carry_tracks=N,
+                    carry_min_score=0.5, candidate_fn=lambda frame: cand, warm=True, landmarks=True,
+                    track_intr=(150.0, 150.0, 63.5, 63.5), lm_min_obs=2, pnp=True, pnp_huber_px=3.0, pnp_weight=1.0)
+        return [r for lo in range(0, T + 5, k) for r in s.push(frames[lo:lo + k])]
+
+    one, three = run(1), run(3)
+    assert [r.frame_index for r in one] == [r.frame_index for r in three] == list(range(6))
+    assert all(bool((r.track_src >= 0).any()) for r in one[1:]), "no track was carried: the hops would share no state"
+    for a, b in zip(one, three):
+        for name in StreamResult._fields + tuple(StreamResult.__annotations__):
+            x, y = getattr(a, name), getattr(b, name)
+            assert x is not None and y is not None, name
+            if torch.is_tensor(x):  # (the bits: an unsolved frame's +inf or a NaN compares as itself)
+                x, y = x.contiguous().view(torch.uint8), y.contiguous().view(torch.uint8)
+                assert torch.equal(x, y), (a.frame_index, name)
+            else:
+                assert x == y, (a.frame_index, name)

@@ -423,6 +423,7 @@ def main():
         print("stream_bench: no GPU", file=sys.stderr)
         return 2
     from comet_amd import functional as F
+    from comet_amd import ops
     from comet_amd.config import instantiate, load_config
     from comet_amd.stream import PoseStream
     T, S, N = args.frames, args.image, args.tracks
@@ -473,12 +474,14 @@ def main():
             return model(frames[None, k:k + T], training=False, tracks=tracks)
 
     stream.push(frames[:T - 1], query_points=q)
+    pairs = [(r, w) for r, w in zip(stream._rings, stream._wins) if r is not None]  # the gather of one window
     ta, tb, tc, err = [], [], [], 0.0
     for k in range(args.warmup + args.hops):
         ms_a, res = timed(lambda: stream.push(frames[k + T - 1], query_points=q))
         ms_b, ref = timed(lambda: closed(k))
         assert len(res) == 1 and res[0].frame_index == k
-        ms_c, _ = timed(lambda: [stream._gather(k % stream.sched.capacity) for _ in range(GATHER_REPS)])
+        table = stream._pool._table(stream.sched.window_slots(k % stream.sched.capacity))
+        ms_c, _ = timed(lambda: [ops.ring_gather(pairs, *table) for _ in range(GATHER_REPS)])
         ms_c /= GATHER_REPS
         if k >= args.warmup:
             ta.append(ms_a)
