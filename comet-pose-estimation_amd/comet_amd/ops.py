@@ -511,10 +511,7 @@ def colsum(x2d, out=None, accumulate=False):
     return out
 
 
-def conv2d_nhwc(x, w, kh, kw, stride, pad, bias=None, act=L.ACT_NONE, resid=None, beta=1.0, out=None,
-                out_dtype=None):
-    """Implicit-GEMM conv (comet_conv2d_nhwc). x [n,h,w,c] bf16 (c % 8 == 0), w [cout, ldw] bf16 with
-    columns (ky, kx, ci). Returns y [n, oh, ow, cout]."""
+def _conv_args(x, w, kh, kw, stride, pad, bias, act, resid, beta, out, out_dtype):
     _req_cuda(x, w, bias, resid)
     n, h, wd, c = x.shape
     cout = w.shape[0]
@@ -533,12 +530,33 @@ def conv2d_nhwc(x, w, kh, kw, stride, pad, bias=None, act=L.ACT_NONE, resid=None
     a.y, a.ldy = _p(out), cout
     a.resid, a.ldr, a.beta = _p(resid), (cout if resid is not None else 0), beta
     a.act = act
+    return a, x, out
+
+
+def conv2d_nhwc(x, w, kh, kw, stride, pad, bias=None, act=L.ACT_NONE, resid=None, beta=1.0, out=None,
+                out_dtype=None):
+    """Implicit-GEMM conv (comet_conv2d_nhwc). x [n,h,w,c] bf16 (c % 8 == 0), w [cout, ldw] bf16 with
+    columns (ky, kx, ci). Returns y [n, oh, ow, cout]."""
+    a, x, out = _conv_args(x, w, kh, kw, stride, pad, bias, act, resid, beta, out, out_dtype)
+    n, h, wd, c = x.shape
+    _, oh, ow, cout = out.shape
     e0 = PROF.start()
     L.check(L.load().comet_conv2d_nhwc(ctypes.byref(a), stream()), "comet_conv2d_nhwc")
     if e0 is not None:
         name = f"conv {kh}x{kw}s{stride} c{c}->{cout} {h}x{wd} n{n}" if PROF.detail else "comet_conv2d_nhwc"
         PROF.stop(e0, name, 2.0 * n * oh * ow * cout * kh * kw * c)
     return out
+
+
+def conv_plan(x, w, kh, kw, stride, pad, bias=None, act=L.ACT_NONE, resid=None, beta=1.0, out=None,
+              out_dtype=None):
+    """The kernel conv2d_nhwc would launch for the same arguments (comet_conv_plan; launches nothing):
+    (kind, NT16, KC, wide) with kind 0 = 128 x 128 implicit GEMM, 1 = 128 x 64, 2 = narrow-output
+    kernel (its NT16 / KC template values and its 16-byte-store flag), 3 = 3x3 rows in LDS."""
+    a, x, out = _conv_args(x, w, kh, kw, stride, pad, bias, act, resid, beta, out, out_dtype)
+    plan = (ctypes.c_int32 * 4)()
+    L.check(L.load().comet_conv_plan(ctypes.byref(a), plan), "comet_conv_plan")
+    return tuple(plan)
 
 
 def im2col_nhwc(x, kh, kw, stride, pad, out_dtype=None, ldc=None):

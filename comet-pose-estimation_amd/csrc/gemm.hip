@@ -2685,29 +2685,49 @@ conv_skinny_kernel(const __bf16* __restrict__ X, int H, int W, int Cin, int KW, 
   }
 }
 
+// Which kernel a convolution runs on: the one decision launch_conv and comet_conv_plan share.
+// kind: 0 = 128 x 128 implicit GEMM, 1 = 128 x 64 implicit GEMM, 2 = narrow-output kernel
+// (conv_skinny_kernel<TC, nt16, kc>, wide: its 16-B bf16 stores), 3 = 3x3 rows in LDS.
+struct ConvPlan {
+  int kind, nt16, kc, wide;
+};
+
+// KC of the conv_skinny_kernel<TC, NT16, KC> instance that holds kcs 32-element k chunks; 0 when
+// there is none (the caller then takes the implicit GEMM). NT16 <= 2: up to 16 chunks; NT16 = 4:
+// up to 8, and 13 for the BasicEncoder's 7x7 stem; NT16 = 3: up to 8.
+inline int conv_skinny_kc(int nt16, int64_t kcs) {
+  for (int kc : {1, 2, 3, 4, 6, 8})
+    if (kcs <= kc) return kc;
+  if (nt16 <= 2) return kcs <= 9 ? 9 : kcs <= 16 ? 16 : 0;
+  if (nt16 == 4 && kcs <= 13) return 13;
+  return 0;
+}
+
 template <typename TC>
-int launch_conv_skinny(const comet_conv_args& a, int64_t M, int OH, int OW, int K, hipStream_t s) {
+int launch_conv_skinny(const comet_conv_args& a, const ConvPlan& p, int64_t M, int OH, int OW, int K, hipStream_t s) {
   Epi e{a.bias, a.bias ? 1 : 0, 0, 0, a.resid, a.ldr, 0, 0, a.beta, nullptr, 0, 0, 0, 1.f, a.act, 0};
-  e.wide = a.cout % 32 == 0 && (uintptr_t)a.y % 16 == 0 && a.ldy % 8 == 0 && getenv("COMET_CONV_NO_WIDE") == nullptr;
+  e.wide = p.wide;
   COMET_CHECK_ARG(M + 64 < (1ll << 31), "comet_conv2d_nhwc (narrow): too many output pixels");
   int64_t blocks = cdiv(cdiv(M, 16), 4 * 8);
   if (blocks > 4096) blocks = 4096;
-  const int nt = (int)(a.cout / 16), kc = (int)cdiv(K, 32);
+  bool launched = true;
 #define CSK(NT, KC)                                                                                        \
   hipLaunchKernelGGL((conv_skinny_kernel<TC, NT, KC>), dim3((unsigned)blocks), dim3(256), 0, s,           \
                      (const __bf16*)a.x, (int)a.h, (int)a.w, (int)a.c, a.kw, a.stride, a.pad, OH, OW,      \
                      (const __bf16*)a.weight, a.ldw, (TC*)a.y, a.ldy, M, (int)a.cout, K, e)
-#define CSK_K(NT)                                                                                          \
-  do {                                                                                                     \
-    if (kc <= 1) CSK(NT, 1); else if (kc <= 2) CSK(NT, 2); else if (kc <= 3) CSK(NT, 3);                   \
-    else if (kc <= 4) CSK(NT, 4); else if (kc <= 6) CSK(NT, 6); else if (kc <= 8) CSK(NT, 8);              \
-    else if (NT <= 2 && kc <= 9) CSK(NT, 9); else if (NT <= 2 && kc <= 16) CSK(NT, 16);                     \
-  } while (0)
-  if (nt == 1) CSK_K(1); else if (nt == 2) CSK_K(2);
-  else if (nt == 3) { if (kc <= 8) CSK_K(3); }
-  else { if (kc <= 8) CSK_K(4); else if (kc <= 13) CSK(4, 13); }
+#define CSK_C(NT, KC) case 100 * NT + KC: CSK(NT, KC); break
+#define CSK_K(NT) CSK_C(NT, 1); CSK_C(NT, 2); CSK_C(NT, 3); CSK_C(NT, 4); CSK_C(NT, 6); CSK_C(NT, 8)
+  switch (100 * p.nt16 + p.kc) {  // every pair conv_skinny_kc can return
+    CSK_K(1); CSK_C(1, 9); CSK_C(1, 16);
+    CSK_K(2); CSK_C(2, 9); CSK_C(2, 16);
+    CSK_K(3);
+    CSK_K(4); CSK_C(4, 13);
+    default: launched = false;
+  }
 #undef CSK_K
+#undef CSK_C
 #undef CSK
+  COMET_CHECK_ARG(launched, "comet_conv2d_nhwc (narrow): no kernel instance for this plan");
   COMET_CHECK_LAUNCH("comet_conv2d_nhwc (narrow)");
   return COMET_OK;
 }
@@ -2884,6 +2904,30 @@ int launch_conv_rows(const comet_conv_args& a, hipStream_t s) {
 }
 
 template <typename TC>
+ConvPlan conv_plan(const comet_conv_args& a) {
+  if (conv_rows_ok<TC>(a)) return ConvPlan{3, 0, 0, 0};
+  const int64_t oh = (a.h + 2 * a.pad - a.kh) / a.stride + 1, ow = (a.w + 2 * a.pad - a.kw) / a.stride + 1;
+  const int64_t M = a.n * oh * ow, K = (int64_t)a.kh * a.kw * a.c;
+  // narrow outputs: weights fit the registers (cout/16 x ceil(K/32) fragments <= 32)
+  const int64_t kcs = cdiv(K, 32);
+  // (and the BasicEncoder's 7x7 stem, cout 64 x K 392: 52 fragments, 208 registers at one wave per SIMD)
+  const bool stem = a.cout == 64 && kcs > 8 && kcs <= 13 && getenv("COMET_CONV_NO_STEM") == nullptr;
+  if (a.cout % 16 == 0 && a.cout <= 64 && ((a.cout / 16) * kcs <= 32 || stem) && kcs <= 16 && M >= 16384 &&
+      (uintptr_t)a.y % (4 * sizeof(TC)) == 0 && a.ldy % 4 == 0 && getenv("COMET_CONV_NO_SKINNY") == nullptr &&
+      (a.resid == nullptr || ((uintptr_t)a.resid % (4 * sizeof(TC)) == 0 && a.ldr % 4 == 0))) {
+    const int nt16 = (int)(a.cout / 16), kc = conv_skinny_kc(nt16, kcs);
+    // (cout 48 with 9 or 10 chunks passes the fragment budget but has no instance: implicit GEMM)
+    if (kc != 0) {
+      const bool wide = std::is_same<TC, __bf16>::value && a.cout % 32 == 0 && (uintptr_t)a.y % 16 == 0 &&
+                        a.ldy % 8 == 0 && getenv("COMET_CONV_NO_WIDE") == nullptr;
+      return ConvPlan{2, nt16, kc, wide ? 1 : 0};
+    }
+  }
+  // 4 x 1 waves over 128 x 64: no zero columns
+  return ConvPlan{(a.cout <= 64 && getenv("COMET_CONV_NO_N64") == nullptr) ? 1 : 0, 0, 0, 0};
+}
+
+template <typename TC>
 int launch_conv(const comet_conv_args& a, hipStream_t s) {
   const int64_t oh = (a.h + 2 * a.pad - a.kh) / a.stride + 1, ow = (a.w + 2 * a.pad - a.kw) / a.stride + 1;
   const int64_t M = a.n * oh * ow, N = a.cout, K = (int64_t)a.kh * a.kw * a.c;
@@ -2894,17 +2938,11 @@ int launch_conv(const comet_conv_args& a, hipStream_t s) {
   Epi e{a.bias, a.bias ? 1 : 0, 0, 0, a.resid, a.ldr, 0, 0, a.beta, nullptr, 0, 0, 0, 1.f, a.act, vec};
   bf::ConvGeo g{reinterpret_cast<const __bf16*>(a.x), (int)a.h, (int)a.w, (int)a.c, a.kw, a.stride, a.pad,
                 (int)oh, (int)ow};
-  if (conv_rows_ok<TC>(a)) return launch_conv_rows<TC>(a, s);
-  // narrow outputs: weights fit the registers (cout/16 x ceil(K/32) fragments <= 32)
-  const int64_t kcs = cdiv(K, 32);
-  // (and the BasicEncoder's 7x7 stem, cout 64 x K 392: 52 fragments, 208 registers at one wave per SIMD)
-  const bool stem = a.cout == 64 && kcs > 8 && kcs <= 13 && getenv("COMET_CONV_NO_STEM") == nullptr;
-  if (a.cout % 16 == 0 && a.cout <= 64 && ((a.cout / 16) * kcs <= 32 || stem) && kcs <= 16 && M >= 16384 &&
-      (uintptr_t)a.y % (4 * sizeof(TC)) == 0 && a.ldy % 4 == 0 && getenv("COMET_CONV_NO_SKINNY") == nullptr &&
-      (a.resid == nullptr || ((uintptr_t)a.resid % (4 * sizeof(TC)) == 0 && a.ldr % 4 == 0)))
-    return launch_conv_skinny<TC>(a, M, (int)oh, (int)ow, (int)K, s);
+  const ConvPlan p = conv_plan<TC>(a);
+  if (p.kind == 3) return launch_conv_rows<TC>(a, s);
+  if (p.kind == 2) return launch_conv_skinny<TC>(a, p, M, (int)oh, (int)ow, (int)K, s);
   Split sp{nullptr, K};
-  if (N <= 64 && getenv("COMET_CONV_NO_N64") == nullptr)  // 4 x 1 waves over 128 x 64: no zero columns
+  if (p.kind == 1)
     hipLaunchKernelGGL((bf::gemm_bf16_kernel<TC, 0, 0, bf::K_BF16_VEC, bf::K_BF16_VEC, false, true, true>),
                        dim3((unsigned)(tiles_m * tiles_n), 1, 1), dim3(NT), 0, s,
                        nullptr, 0, 0, 0, reinterpret_cast<const __bf16*>(a.weight), a.ldw, 0, 0,
@@ -2918,12 +2956,8 @@ int launch_conv(const comet_conv_args& a, hipStream_t s) {
   return COMET_OK;
 }
 
-}  // namespace
-
-}  // namespace comet
-
-extern "C" int comet_conv2d_nhwc(const comet_conv_args* args, void* stream) {
-  using namespace comet;
+// argument checks shared by comet_conv2d_nhwc and comet_conv_plan (host only)
+int validate_conv(const comet_conv_args* args) {
   COMET_CHECK_ARG(args != nullptr, "comet_conv2d_nhwc: null args");
   const comet_conv_args& a = *args;
   COMET_CHECK_ARG(a.dtype == COMET_BF16, "comet_conv2d_nhwc: x/weight must be bf16 (use im2col + comet_gemm for f32)");
@@ -2935,11 +2969,34 @@ extern "C" int comet_conv2d_nhwc(const comet_conv_args* args, void* stream) {
   COMET_CHECK_ARG(a.x && a.weight && a.y, "comet_conv2d_nhwc: null pointer");
   COMET_CHECK_ARG((uintptr_t)a.x % 16 == 0 && (uintptr_t)a.weight % 16 == 0, "comet_conv2d_nhwc: x/weight must be 16-byte aligned");
   COMET_CHECK_ARG(a.n * a.h * a.w * a.c < (1ll << 40), "comet_conv2d_nhwc: input too large");
+  COMET_CHECK_ARG(a.dtype_y == COMET_BF16 || a.dtype_y == COMET_F32, "comet_conv2d_nhwc: bad dtype_y");
+  return COMET_OK;
+}
+
+}  // namespace
+
+}  // namespace comet
+
+extern "C" int comet_conv2d_nhwc(const comet_conv_args* args, void* stream) {
+  using namespace comet;
+  const int rc = validate_conv(args);
+  if (rc != COMET_OK) return rc;
   hipStream_t s = as_stream(stream);
-  if (a.dtype_y == COMET_BF16) return launch_conv<__bf16>(a, s);
-  if (a.dtype_y == COMET_F32) return launch_conv<float>(a, s);
-  set_error("comet_conv2d_nhwc: bad dtype_y");
-  return COMET_EINVAL;
+  if (args->dtype_y == COMET_BF16) return launch_conv<__bf16>(*args, s);
+  return launch_conv<float>(*args, s);
+}
+
+extern "C" int comet_conv_plan(const comet_conv_args* args, int32_t* plan) {
+  using namespace comet;
+  const int rc = validate_conv(args);
+  if (rc != COMET_OK) return rc;
+  COMET_CHECK_ARG(plan != nullptr, "comet_conv_plan: null plan");
+  const ConvPlan p = args->dtype_y == COMET_BF16 ? conv_plan<__bf16>(*args) : conv_plan<float>(*args);
+  plan[0] = p.kind;
+  plan[1] = p.nt16;
+  plan[2] = p.kc;
+  plan[3] = p.wide;
+  return COMET_OK;
 }
 
 extern "C" int comet_gemm_workspace(const comet_gemm_args* args, int64_t* bytes) {

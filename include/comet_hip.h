@@ -146,6 +146,13 @@ typedef struct comet_conv_args {
 } comet_conv_args;
 
 int comet_conv2d_nhwc(const comet_conv_args* args, void* stream);
+/* The kernel comet_conv2d_nhwc will launch for these arguments (host only, launches nothing; the
+ * launcher takes the same decision function): plan[0] = 0 128 x 128 implicit GEMM, 1 128 x 64
+ * implicit GEMM (cout <= 64), 2 narrow-output kernel (cout <= 64 in 16s, weights in registers,
+ * >= 16384 output pixels), 3 3x3 rows in LDS (c = cout = 64); for kind 2, plan[1] = its NT16
+ * (cout / 16), plan[2] = its KC template value (32-element k chunks held), plan[3] = 1 when it
+ * stores 16 bytes per lane (bf16 output, cout % 32 == 0); 0 otherwise. */
+int comet_conv_plan(const comet_conv_args* args, int32_t* plan);
 
 /* ---------------------------------------------------------------------------------------
  * Row LayerNorm over the last dim (nn.LayerNorm; also GroupNorm(1, C) on [rows, C] as used
