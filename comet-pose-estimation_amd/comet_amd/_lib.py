@@ -96,6 +96,9 @@ FUSE_ROW = 20         # COMET_FUSE_ROW: doubles per accumulator row of comet_pos
 CARRY_MAX_TRACKS, CARRY_MAX_CANDIDATES, CARRY_MAX_CELLS = 4096, 65536, 8192  # COMET_CARRY_MAX_*
 LM_ROW = 12           # COMET_LM_ROW: doubles per accumulator row of comet_landmark_update
 PNP_MAX_ITERS = 16    # COMET_PNP_MAX_ITERS: Gauss-Newton steps of comet_landmark_pnp
+MOTION_ROW = 8        # COMET_MOTION_ROW: doubles per history row of comet_motion_fit
+MOTION_MAX_CAP, MOTION_MAX_ITERS, MOTION_MAX_HORIZON = 64, 8, 64  # the wave width, COMET_MOTION_MAX_*
+MOTION_COUNT_FOLD = 1 << 30  # COMET_MOTION_COUNT_FOLD: where hist_n of comet_motion_fit saturates
 
 # (name, restype, argtypes); every exported symbol of include/comet_hip.h
 _F = ctypes.c_float
@@ -202,6 +205,7 @@ SIGNATURES = {
                                   ctypes.c_double, _INT, ctypes.c_double, c_vp, _INT, c_vp, c_vp, ctypes.c_double,
                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp,
                                   c_vp, c_vp, c_vp, c_vp]),
+    "comet_motion_fit": (_INT, [c_vp] * 8 + [_INT] * 9 + [ctypes.c_double, _INT] + [c_vp] * 13),
 }
 
 _lib = None

@@ -717,6 +717,44 @@ def _log_pnp(logger, hop, r, stride):
     logger.log(dict(zip(PNP_FIELDS, vals + r.pnp_R[i].double().tolist() + r.pnp_T[i].double().tolist())))
 
 
+# cfg.stream.motion: one more CSV per sequence, one row per hop
+MOTION_FIELDS = ("hop", "frame", "state", "frames", "wx", "wy", "wz", "vx", "vy", "vz", "qw", "qx", "qy", "qz", "tx", "ty",
+                 "tz", "rot_rms", "trans_rms_x", "trans_rms_y", "trans_rms_z", "innov_rot", "innov_trans")
+
+
+def _stream_motion(cfg, fuse):
+    """cfg.stream.motion (default false) / motion_len (16) / motion_min_frames (3) / motion_iters (2) /
+    motion_horizon (1) / motion_max_angle (2.0 rad) / motion_inverse_rotation (0), all stated values, not tuned
+    ones -> the motion keywords of PoseStream / StreamPool ({} with motion off)."""
+    if not _get(cfg, "stream.motion", False):
+        return {}
+    if not fuse:
+        raise ValueError("cfg.stream.motion needs cfg.stream.fuse: the motion is fitted to the final fused poses")
+    return dict(motion=True, motion_len=int(_get(cfg, "stream.motion_len", 16)),
+                motion_min_frames=int(_get(cfg, "stream.motion_min_frames", 3)),
+                motion_iters=int(_get(cfg, "stream.motion_iters", 2)),
+                motion_horizon=int(_get(cfg, "stream.motion_horizon", 1)),
+                motion_max_angle=float(_get(cfg, "stream.motion_max_angle", 2.0)),
+                motion_inverse_rotation=int(_get(cfg, "stream.motion_inverse_rotation", 0)))
+
+
+def motion_csv(csv_path):
+    """The path of the motion CSV that goes with the hop CSV csv_path: <stem>_motion.csv."""
+    stem, ext = os.path.splitext(csv_path)
+    return stem + "_motion" + ext
+
+
+def _log_motion(logger, hop, r):
+    """One row of the motion CSV (MOTION_FIELDS) for a hop's StreamResult: `frame` is the newest frame whose
+    fused pose is final, where q / t (the fitted pose) and the rates (rad / frame, per frame) apply;
+    innov_* is the innovation on the frame after it (+inf, like the rms columns, where state != 1)."""
+    vals = [hop, r.frame_index + r.final - 1, int(r.motion_state), int(r.motion_frames)]
+    vals += r.motion_omega.tolist() + r.motion_vel.tolist() + r.motion_q0.tolist() + r.motion_t0.tolist()
+    vals += [float(r.motion_rot_rms)] + r.motion_trans_rms.double().tolist()
+    vals += [float(r.motion_innov_rot[0]), float(r.motion_innov_trans[0])]
+    logger.log(dict(zip(MOTION_FIELDS, vals)))
+
+
 def _track_intr(dataset, box, size):
     """(fx, fy, cx, cy) of the pixels the tracks of a sequence live in: the dataset's intrinsics mapped
     into the crop `box` resized to size x size, the frames stream_eval pushes."""
@@ -810,7 +848,10 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
     lm_gate_px and lm_inverse_rotation) turns the landmark map on (PoseStream landmarks=True) with the
     intrinsics of the anchor's dataset mapped into `box` (data.crop_intrinsics); the hop CSV is what it
     was, and at the end of the stream landmarks_csv(csv_path) takes the final snapshot, one row per valid
-    live landmark (LANDMARK_FIELDS)."""
+    live landmark (LANDMARK_FIELDS).
+    cfg.stream.motion (default false; needs fuse; with motion_len, motion_min_frames, motion_iters,
+    motion_horizon, motion_max_angle and motion_inverse_rotation) turns the motion estimate on (PoseStream
+    motion=True); the hop CSV is what it was, and motion_csv(csv_path) takes one row per hop (MOTION_FIELDS)."""
     from .data import crop_resize_normalize
     from .stream import PoseStream, keypoint_query
     if not _get(cfg, "stream.enable", False):
@@ -827,16 +868,18 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
     fuse, fuse_weight, anchor, fields = _stream_fuse(cfg, anchor)
     lm = _stream_landmarks(cfg, fuse, carry)
     pnp = _stream_pnp(cfg, lm)
+    motion = _stream_motion(cfg, fuse)
     if lm:
         lm["track_intr"] = _track_intr(anchor[4], box, size)
     stream = PoseStream(model, window=window, stride=int(_get(cfg, "stream.stride", 1)),
                         capacity=_get(cfg, "stream.capacity", None), query_fn=query_fn, anchor=anchor,
                         precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight,
-                        **carry, **lm, **pnp)
+                        **carry, **lm, **pnp, **motion)
     if carry:
         fields = tuple(fields) + _carry_fields(carry)
     logger = CsvLogger(csv_path, fields)
     pnp_logger = CsvLogger(pnp_csv(csv_path), PNP_FIELDS) if pnp else None
+    motion_logger = CsvLogger(motion_csv(csv_path), MOTION_FIELDS) if motion else None
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     hops, last = 0, None
     for frame in frames_iter:
@@ -849,6 +892,8 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
             last = (r, _log_hop(logger, fields, r, window, e0.elapsed_time(e1)))
             if pnp:
                 _log_pnp(pnp_logger, hops, r, stream.landmark_map.stride)
+            if motion:
+                _log_motion(motion_logger, hops, r)
             hops += 1
     if fuse and last is not None:
         _log_hop(logger, fields, last[0], window, None, last=last[1])
@@ -873,7 +918,9 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
     carry=True; a sequence that takes over a stream starts with fresh ids). cfg.stream.warm, warm_mode and
     warm_iters: as stream_eval (StreamPool warm=True). cfg.stream.landmarks and lm_*: as stream_eval
     (StreamPool landmarks=True): a sequence that takes over a stream brings the intrinsics of its own box
-    and starts with an empty map, and when it ends csv_dir/<name>_landmarks.csv takes its final snapshot."""
+    and starts with an empty map, and when it ends csv_dir/<name>_landmarks.csv takes its final snapshot.
+    cfg.stream.motion and motion_*: as stream_eval (StreamPool motion=True): a sequence that takes over a stream
+    starts with an empty history, and csv_dir/<name>_motion.csv takes one row per hop."""
     from .data import crop_resize_normalize
     from .stream import StreamPool, keypoint_query
     if not _get(cfg, "stream.enable", False):
@@ -895,6 +942,7 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
         raise ValueError("stream_eval_pool: anchors without cfg.stream.fuse are not supported")
     lm = _stream_landmarks(cfg, fuse, carry)
     pnp = _stream_pnp(cfg, lm)
+    motion = _stream_motion(cfg, fuse)
     if lm:  # (the uncropped intrinsics stand in until reset(sid, track_intr=...) brings each sequence's own)
         from .models.utils import INTRINSICS
         lm["track_intrs"] = [INTRINSICS[default_anchor[4]]] * S
@@ -902,10 +950,11 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
                       capacity=_get(cfg, "stream.capacity", None), query_fn=query_fn,
                       anchors=[default_anchor] * S if fuse else None,
                       precision=torch.bfloat16 if mp == "bf16" else torch.float32, fuse=fuse, fuse_weight=fuse_weight,
-                      **carry, **lm, **pnp)
+                      **carry, **lm, **pnp, **motion)
     if carry:
         fields = tuple(fields) + _carry_fields(carry)
     pnp_loggers = {}  # sequence name -> the logger of its <name>_pnp.csv
+    motion_loggers = {}  # sequence name -> the logger of its <name>_motion.csv
     lasts = {}  # stream id -> (last result, its row): flushed when the sequence ends
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     seqs = iter(sequences)
@@ -926,6 +975,8 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
                 hops[name] = 0
                 if pnp:
                     pnp_loggers[name] = CsvLogger(pnp_csv(running[sid][3].path), PNP_FIELDS)
+                if motion:
+                    motion_loggers[name] = CsvLogger(motion_csv(running[sid][3].path), MOTION_FIELDS)
             frame = next(running[sid][1], None)
             if frame is not None:
                 return frame
@@ -951,6 +1002,8 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
             lasts[sid] = (r, _log_hop(logger, fields, r, window, e0.elapsed_time(e1)))
             if pnp:
                 _log_pnp(pnp_loggers[name], hops[name], r, pool.landmark_map.stride)
+            if motion:
+                _log_motion(motion_loggers[name], hops[name], r)
             hops[name] += 1
 
 

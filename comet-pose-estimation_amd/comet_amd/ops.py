@@ -912,6 +912,66 @@ def landmark_pnp(tracks, X, state, R, T, intr, intr_host, s, huber_px, weights=N
     return out
 
 
+class MotionOut(NamedTuple):
+    omega: torch.Tensor        # [n, 3] f64 angular velocity, rad / frame: R(tau) = Exp(omega tau) R0
+    q0: torch.Tensor           # [n, 4] f64 fitted rotation at the newest committed frame (unit, w >= 0)
+    vel: torch.Tensor          # [n, 3] f64 linear velocity, per frame
+    t0: torch.Tensor           # [n, 3] f64 fitted translation at the newest committed frame
+    rot_rms: torch.Tensor      # [n] f32 weighted rms of the rotation residuals, rad (+inf where state != 1)
+    trans_rms: torch.Tensor    # [n, 3] f32 weighted rms of the translation residuals (+inf where state != 1)
+    n_used: torch.Tensor       # [n] int32 rows the fit used
+    state: torch.Tensor        # [n] int32: 1 fitted, 0 too few frames, 2 degenerate, 3 beyond max_angle, -1 not finite
+    pred_q: torch.Tensor       # [n, P, 4] f64 predicted rotations, 1 .. P = T - s + horizon frames ahead
+    pred_t: torch.Tensor       # [n, P, 3] f64 predicted translations
+    innov_rot: torch.Tensor    # [n, T - s] f32 angle between the fused and the predicted rotation, positions [s, T)
+    innov_trans: torch.Tensor  # [n, T - s] f32 distance between the fused and the predicted translation
+
+
+def motion_fit(R, T, first, stream_idx, stream_idx_host, hist, hist_n, s, weights=None, fit_len=16, min_frames=3,
+               iters=2, horizon=1, max_angle=2.0, inverse_rotation=0):
+    """comet_motion_fit (include/comet_hip.h): the n hops with the fused poses R [n, T, 4] f32 / T [n, T, 3]
+    f64 commit their first s frames to the history hist [S, cap, 8] f64 / hist_n [S] int32 in place and a
+    constant angular and linear velocity is fitted to the newest fit_len frames of each -> MotionOut, all in
+    one launch. first [n] int32 (1: the stream's history starts over) and stream_idx [n] int32 on the device,
+    stream_idx_host the same values as a ctypes int32 array (checked by the library before it launches);
+    weights [n, T] f32 or None (= 1)."""
+    _req_cuda(R, T, first, stream_idx, hist, hist_n, weights)
+    if R.dim() != 3 or R.shape[2] != 4 or R.dtype != torch.float32 or not R.is_contiguous():
+        raise L.CometHipError(f"motion_fit: R must be a dense f32 [n, T, 4] tensor, got {tuple(R.shape)} {R.dtype}")
+    n, Tw = R.shape[:2]
+    for name, t, shape, dtype in (("T", T, (n, Tw, 3), torch.float64), ("first", first, (n,), torch.int32),
+                                  ("stream_idx", stream_idx, (n,), torch.int32),
+                                  ("weights", weights, (n, Tw), torch.float32)):
+        if t is not None and (t.shape != shape or t.dtype != dtype or not t.is_contiguous()):
+            raise L.CometHipError(f"motion_fit: {name} must be a dense {dtype} {list(shape)} tensor")
+    if hist.dim() != 3 or hist.shape[2] != L.MOTION_ROW or hist.dtype != torch.float64 or not hist.is_contiguous():
+        raise L.CometHipError(f"motion_fit: hist must be a dense f64 [S, cap, {L.MOTION_ROW}] tensor")
+    if hist_n.shape != (hist.shape[0],) or hist_n.dtype != torch.int32 or not hist_n.is_contiguous():
+        raise L.CometHipError("motion_fit: hist_n must be a dense int32 [S] tensor")
+    if len(stream_idx_host) != n:
+        raise L.CometHipError("motion_fit: stream_idx_host needs n entries")
+    dev = R.device
+    if any(t is not None and t.device != dev for t in (T, first, stream_idx, hist, hist_n, weights)):
+        raise L.CometHipError("motion_fit: every tensor must be on one device")
+    s, horizon = int(s), int(horizon)
+    P, I = max(Tw - s + horizon, 1), max(Tw - s, 1)  # (a bad s or horizon is the library's to report)
+    f64 = dict(device=dev, dtype=torch.float64)
+    out = MotionOut(torch.empty(n, 3, **f64), torch.empty(n, 4, **f64), torch.empty(n, 3, **f64), torch.empty(n, 3, **f64),
+                    torch.empty(n, device=dev), torch.empty(n, 3, device=dev),
+                    torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=torch.int32),
+                    torch.empty(n, P, 4, **f64), torch.empty(n, P, 3, **f64), torch.empty(n, I, device=dev),
+                    torch.empty(n, I, device=dev))
+    e0 = PROF.start()
+    L.check(L.load().comet_motion_fit(_p(R), _p(T), _p(weights), _p(first), _p(stream_idx),
+                                      ctypes.addressof(stream_idx_host), _p(hist), _p(hist_n), hist.shape[0],
+                                      hist.shape[1], n, Tw, s, int(fit_len), int(min_frames), int(iters), horizon,
+                                      float(max_angle), int(inverse_rotation), *[_p(t) for t in out], stream()),
+            "motion_fit")
+    if e0 is not None:
+        PROF.stop(e0, "comet_motion_fit", 0.0, float(n * (8 * L.MOTION_ROW * (s + int(fit_len)) + Tw * 40 + P * 56 + 200)))
+    return out
+
+
 def resize_bilinear_pool(x, oh, ow):
     """NHWC x [n, h, w, c] -> (y [n, oh, ow, c] bilinear, align_corners=True; its 2 x 2 average
     pool [n, oh // 2, ow // 2, c]) in one kernel: resize_bilinear + avgpool2_nhwc bit for bit."""

@@ -22,10 +22,13 @@ them once per frame, keeps their outputs in device rings, and for every hop gath
                  the coarse tracker starts in the new window (comet_track_warm, one launch per push)
   LandmarkMap    one 3-D point per carried track, triangulated from the frames whose fused pose is final
                  (comet_landmark_update, one launch per push)
+  MotionTracker  the target's angular and linear velocity from the final fused poses, with predictions for the
+                 next frames (comet_motion_fit, one launch per push)
   keypoint_query query_fn from the SuperPoint / SIFT detectors of comet_amd.keypoints
   keypoint_candidates  candidate_fn of the same detectors for carry=True: raw detections, no padding
 """
 import ctypes
+import math
 from typing import NamedTuple, Optional
 
 import torch
@@ -121,6 +124,20 @@ class StreamResult(_StreamFields):
     pnp_inliers: Optional[torch.Tensor] = None  # [T] int32 landmarks within pnp_huber_px at the refined pose
     pnp_rms_px: Optional[torch.Tensor] = None   # [T] f32 weighted rms reprojection error (+inf where pnp_state != 1)
     pnp_state: Optional[torch.Tensor] = None    # [T] int32: 1 solved, 0 too few landmarks, 2 degenerate, -1 not finite
+    # motion=True only (MotionTracker; attributes too): a constant-rate fit to the final fused poses so far.
+    # (Plain class attributes: the annotated fields above end with the PnP ones.)
+    motion_omega = None      # [3] float64 rad / frame, camera frame: R(tau) = Exp(omega tau) R0
+    motion_vel = None        # [3] float64 per frame
+    motion_q0 = None         # [4] float64 fitted rotation at the newest final frame
+    motion_t0 = None         # [3] float64 fitted translation at the newest final frame
+    motion_rot_rms = None    # [] f32 rad (+inf where motion_state != 1)
+    motion_trans_rms = None  # [3] f32 (+inf where motion_state != 1)
+    motion_frames = None     # [] int32 frames the fit used
+    motion_state = None      # [] int32: 1 fitted, 0 too few, 2 degenerate, 3 too fast, -1 not finite
+    motion_pred_R = None     # [T - stride + horizon, 4] float64, 1, 2, .. frames past the newest final one
+    motion_pred_T = None     # [T - stride + horizon, 3] float64
+    motion_innov_rot = None    # [T - stride] f32 rad: fused against predicted, positions [stride, T)
+    motion_innov_trans = None  # [T - stride] f32
 
     def _replace(self, **kw):
         r = super()._replace(**kw)
@@ -142,6 +159,16 @@ class StreamResult(_StreamFields):
         """The result with row b of an ops.PnpOut."""
         r = self._replace()
         r.pnp_R, r.pnp_T, r.pnp_inliers, r.pnp_rms_px, r.pnp_state = po.R[b], po.T[b], po.inliers[b], po.rms_px[b], po.state[b]
+        return r
+
+    def with_motion(self, mo, b):
+        """The result with row b of an ops.MotionOut."""
+        r = self._replace()
+        r.motion_omega, r.motion_vel, r.motion_q0, r.motion_t0 = mo.omega[b], mo.vel[b], mo.q0[b], mo.t0[b]
+        r.motion_rot_rms, r.motion_trans_rms, r.motion_frames, r.motion_state = (mo.rot_rms[b], mo.trans_rms[b],
+                                                                                 mo.n_used[b], mo.state[b])
+        r.motion_pred_R, r.motion_pred_T = mo.pred_q[b], mo.pred_t[b]
+        r.motion_innov_rot, r.motion_innov_trans = mo.innov_rot[b], mo.innov_trans[b]
         return r
 
 
@@ -786,6 +813,124 @@ class LandmarkMap:
         return ids[b][on], out.X[b][on], out.n_obs[b][on]
 
 
+def _check_motion(motion, fuse, motion_len, motion_min_frames, motion_iters, motion_horizon, motion_max_angle,
+                  motion_inverse_rotation):
+    """-> the keywords of MotionTracker, or None with motion off."""
+    if not motion:
+        return None
+    if not fuse:
+        raise ValueError("motion=True needs fuse=True: the motion is fitted to the final fused poses")
+    if not 2 <= int(motion_len) <= L.MOTION_MAX_CAP:
+        raise ValueError(f"motion_len must be 2 to {L.MOTION_MAX_CAP} frames, got {motion_len}")
+    if not 2 <= int(motion_min_frames) <= int(motion_len):
+        raise ValueError(f"motion_min_frames must be 2 to motion_len = {motion_len}, got {motion_min_frames}")
+    if not 1 <= int(motion_iters) <= L.MOTION_MAX_ITERS:
+        raise ValueError(f"motion_iters must be 1 to {L.MOTION_MAX_ITERS}, got {motion_iters}")
+    if not 0 <= int(motion_horizon) <= L.MOTION_MAX_HORIZON:
+        raise ValueError(f"motion_horizon must be 0 to {L.MOTION_MAX_HORIZON}, got {motion_horizon}")
+    if not 0.0 < float(motion_max_angle) < math.pi:
+        raise ValueError(f"motion_max_angle must lie in (0, pi) radians, got {motion_max_angle}")
+    if motion_inverse_rotation not in (0, 1, False, True):
+        raise ValueError(f"motion_inverse_rotation must be 0 or 1, got {motion_inverse_rotation}")
+    return dict(fit_len=int(motion_len), min_frames=int(motion_min_frames), iters=int(motion_iters),
+                horizon=int(motion_horizon), max_angle=float(motion_max_angle),
+                inverse_rotation=int(motion_inverse_rotation))
+
+
+class MotionTracker:
+    """The target's angular and linear velocity from the final fused poses (DESIGN.md "Motion estimate").
+
+        mt = MotionTracker(window=T, stride=1, streams=1)
+        fo = fuser.fuse(enc, [(0, hop)])
+        mo = mt.update([(0, hop)], fo)            # ops.MotionOut: omega, vel, q0, t0, predictions, innovations
+
+    Owns the history hist [streams, fit_len, 8] float64 and hist_n [streams] int32 on the device. update() is
+    one comet_motion_fit launch for all the hops given (at most one per stream): `hops` = [(stream, Hop)], the
+    pairs of that push's PoseFuser.fuse() call in its order, and `fused` its ops.FuseOut (or any object with
+    R [n, T, 4] f32 and T [n, T, 3] f64). The first `stride` positions of every window, whose fused pose is
+    final, are appended to the stream's history, and a constant angular velocity (a weighted line through the
+    rotation vectors about a reference the fit re-centres `iters` times) and a constant linear velocity are
+    fitted to its newest fit_len frames. A stream's hops must follow one another: a hop whose first frame is
+    not the stride-th after the previous hop's raises, since the history's time axis is the frame count.
+    reset(stream) forgets that stream's history (its next hop starts a new one).
+
+    fit_len = 16, min_frames = 3, iters = 2, horizon = 1 and max_angle = 2.0 rad are stated values, not tuned
+    ones: nothing here has been measured on real imagery. max_angle bounds the rotation between a frame and the
+    reference inside the fitted span, where a rotation vector stops being a usable coordinate; a faster tumble
+    reports state 3 and no rate. inverse_rotation: as LandmarkMap's. The estimate is reported and fed back
+    into nothing."""
+
+    _TABLES_MAX = 1024
+
+    def __init__(self, window, stride=1, streams=1, fit_len=16, min_frames=3, iters=2, horizon=1, max_angle=2.0,
+                 inverse_rotation=0):
+        if stride < 1 or stride >= window:
+            raise ValueError(f"the motion estimate needs 1 <= stride < window (stride {stride}, window {window})")
+        if streams < 1:
+            raise ValueError(f"at least 1 stream, got {streams}")
+        self._kw = _check_motion(True, True, fit_len, min_frames, iters, horizon, max_angle, inverse_rotation)
+        self.window, self.stride, self.streams = int(window), int(stride), int(streams)
+        self.device = None
+        self._first = [True] * self.streams
+        self._next = [None] * self.streams  # the frame index a stream's next hop must start at
+        self._tables = {}
+
+    def _id(self, stream):
+        s = int(stream)
+        if not 0 <= s < self.streams:
+            raise ValueError(f"unknown stream {s}: the tracker has streams 0 .. {self.streams - 1}")
+        return s
+
+    def _ensure(self, dev):
+        if self.device == dev:
+            return
+        self.device = dev
+        self.hist = torch.zeros(self.streams, self._kw["fit_len"], L.MOTION_ROW, dtype=torch.float64, device=dev)
+        self.hist_n = torch.zeros(self.streams, dtype=torch.int32, device=dev)
+        self._first = [True] * self.streams
+        self._next = [None] * self.streams
+        self._tables = {}
+
+    def _table(self, values):
+        hit = self._tables.get(values)
+        if hit is None:
+            if len(self._tables) >= self._TABLES_MAX:
+                self._tables.clear()
+            hit = self._tables[values] = (torch.tensor(values, dtype=torch.int32, device=self.device),
+                                          (ctypes.c_int32 * len(values))(*values))
+        return hit
+
+    def reset(self, stream=None):
+        """The history of `stream` (default: of every stream) is forgotten: its next hop starts a new one
+        (first = 1 in its launch, which sets hist_n = 0 before it appends; no row needs clearing)."""
+        for s in (range(self.streams) if stream is None else [self._id(stream)]):
+            self._first[s], self._next[s] = True, None
+
+    def update(self, hops, fused, weights=None):
+        """hops = [(stream, Hop)] of distinct streams, fused.R [n, T, 4] f32 / fused.T [n, T, 3] f64 in their
+        order, weights [n, T] f32 or None -> ops.MotionOut."""
+        sids = tuple(self._id(s) for s, _ in hops)
+        n, T = len(sids), self.window
+        if n == 0 or len(set(sids)) != n:
+            raise ValueError(f"update takes at least one hop and one hop per stream, got the streams {list(sids)}")
+        for s, (_, hop) in zip(sids, hops):
+            if not self._first[s] and hop.frame_index != self._next[s]:
+                raise ValueError(f"stream {s}: the hop at frame {hop.frame_index} does not follow the last one (frame "
+                                 f"{self._next[s]} expected): every frame is committed exactly once; reset({s}) "
+                                 "starts a new history")
+        R, Tx = fused.R, fused.T
+        if R.numel() != n * T * 4:
+            raise ValueError(f"{n} hops of window {T} need fused poses [{n}, {T}, ...], got R {tuple(R.shape)}")
+        self._ensure(R.device)
+        idx, idx_host = self._table(sids)
+        first, _ = self._table(tuple(int(self._first[s]) for s in sids))
+        out = ops.motion_fit(R.view(n, T, 4), Tx.view(n, T, 3), first, idx, idx_host, self.hist, self.hist_n,
+                             self.stride, weights, **self._kw)
+        for s, (_, hop) in zip(sids, hops):  # (only a launch that went out advances the bookkeeping)
+            self._first[s], self._next[s] = False, hop.frame_index + self.stride
+        return out
+
+
 def _per_frame(cache):
     """FrameCache of one k-frame sequence -> its tensors as [k, ...] (None where unused)."""
     return [None if cache.fmaps is None else cache.fmaps[0], cache.refine_frames[0], cache.tokens]
@@ -875,6 +1020,20 @@ class PoseStream:
     trajectory that feedback lowers the (u, v, z) drift and raises the rotation drift; accuracy on real
     imagery is unmeasured and no value of these keywords is recommended. With pnp=False nothing changes.
 
+    motion=True (needs fuse=True) estimates how the target moves (MotionTracker, DESIGN.md "Motion estimate"):
+    one comet_motion_fit launch per hop, after the fuse launch, appends the window's first `stride` frames,
+    whose fused pose is final, to a history of motion_len frames and fits a constant angular velocity and a
+    constant linear velocity to it. Results then carry motion_omega [3] (rad / frame, camera frame: R(tau) =
+    Exp(omega tau) R0), motion_vel [3] (per frame), motion_q0 / motion_t0 (the fitted pose at the newest final
+    frame), motion_rot_rms, motion_trans_rms, motion_frames, motion_state (1 fitted; else no rate: omega = vel
+    = 0 and the predictions repeat the newest final pose), motion_pred_R / motion_pred_T (the poses 1 ..
+    window - stride + motion_horizon frames past the newest final frame; the first window - stride of them are
+    the positions [stride, window) of this window) and motion_innov_rot / motion_innov_trans (fused against
+    predicted on those positions). motion_len = 16, motion_min_frames = 3, motion_iters = 2, motion_horizon = 1
+    and motion_max_angle = 2.0 rad are stated values, not tuned ones; motion_inverse_rotation: as
+    lm_inverse_rotation. The estimate is reported only and feeds nothing back; its accuracy on real imagery
+    is unmeasured. With motion=False nothing changes.
+
     One stream (batch 1): a PoseStream is a StreamPool of one stream. push() runs the per-frame stages on
     its k frames as one batch and hands them, frame by frame, to the pool's hop pipeline
     (StreamPool._advance), which is the only implementation of everything above. The model is used as is
@@ -885,7 +1044,8 @@ class PoseStream:
                  carry_min_score=None, detect_every=1, candidate_fn=None, mask_fn=None, warm=False, warm_mode="hold",
                  warm_iters=None, landmarks=False, track_intr=None, lm_min_obs=3, lm_min_pivot=1e-8, lm_weight=None,
                  lm_gate_px=None, lm_inverse_rotation=0, pnp=False, pnp_iters=4, pnp_huber_px=None, pnp_min_pts=6,
-                 pnp_weight=0.0):
+                 pnp_weight=0.0, motion=False, motion_len=16, motion_min_frames=3, motion_iters=2, motion_horizon=1,
+                 motion_max_angle=2.0, motion_inverse_rotation=0):
         self._pool = StreamPool(
             model, 1, window, stride, capacity, query_fn, None if anchor is None else [anchor], precision, fuse=fuse,
             fuse_weight=fuse_weight, carry=carry, carry_tracks=carry_tracks, carry_cell=carry_cell,
@@ -894,15 +1054,18 @@ class PoseStream:
             landmarks=landmarks, track_intrs=None if track_intr is None else [track_intr], lm_min_obs=lm_min_obs,
             lm_min_pivot=lm_min_pivot, lm_weight=lm_weight, lm_gate_px=lm_gate_px,
             lm_inverse_rotation=lm_inverse_rotation, pnp=pnp, pnp_iters=pnp_iters, pnp_huber_px=pnp_huber_px,
-            pnp_min_pts=pnp_min_pts, pnp_weight=pnp_weight)
+            pnp_min_pts=pnp_min_pts, pnp_weight=pnp_weight, motion=motion, motion_len=motion_len,
+            motion_min_frames=motion_min_frames, motion_iters=motion_iters, motion_horizon=motion_horizon,
+            motion_max_angle=motion_max_angle, motion_inverse_rotation=motion_inverse_rotation)
         self.sched = self._pool.sched.scheds[0]  # the stream's own RingSchedule
         self.anchor = None if anchor is None else self._pool.anchors[0]
         self._hw = None  # the frame size push() holds the stream to
 
-    # what a caller reads off a stream is the pool's (landmark_map: the LandmarkMap, or None)
+    # what a caller reads off a stream is the pool's (landmark_map: the LandmarkMap, motion_tracker: the
+    # MotionTracker, or None)
     _POOLED = frozenset(("model", "query_fn", "precision", "fuse", "fuse_weight", "carry", "candidate_fn", "mask_fn",
                          "warm", "warm_mode", "warm_iters", "landmarks", "lm_weight", "lm_gate_px", "pnp", "landmark_map",
-                         "_pnp", "_carry", "_lm", "_fuser", "_rings", "_wins"))
+                         "_pnp", "_carry", "_lm", "_fuser", "_rings", "_wins", "motion", "motion_tracker", "_motion"))
 
     def __getattr__(self, name):
         if name in self._POOLED:
@@ -1055,6 +1218,8 @@ class StreamPool:
     comet_landmark_update launch, after the fuse launch, serves all the hops due in a push (the rows of two
     warm-start calls are stacked first); reset(stream) forgets that stream's landmarks. pnp / pnp_*: as
     PoseStream's; one comet_landmark_pnp launch per push, on the rows of the landmark launch in its order.
+    motion / motion_*: as PoseStream's; one comet_motion_fit launch per push, on the rows of the fuse launch in
+    its order; reset(stream) forgets that stream's history.
 
     push() -> [(stream id, StreamResult)] ordered by stream id. The tensors of a result are views
     of the batched outputs. The model is used as is (its eval / train mode included)."""
@@ -1066,7 +1231,8 @@ class StreamPool:
                  carry_min_score=None, detect_every=1, candidate_fn=None, mask_fn=None, warm=False, warm_mode="hold",
                  warm_iters=None, landmarks=False, track_intrs=None, lm_min_obs=3, lm_min_pivot=1e-8, lm_weight=None,
                  lm_gate_px=None, lm_inverse_rotation=0, pnp=False, pnp_iters=4, pnp_huber_px=None, pnp_min_pts=6,
-                 pnp_weight=0.0):
+                 pnp_weight=0.0, motion=False, motion_len=16, motion_min_frames=3, motion_iters=2, motion_horizon=1,
+                 motion_max_angle=2.0, motion_inverse_rotation=0):
         self.model = model
         self.sched = PoolSchedule(streams, window, stride, capacity)
         _check_landmarks(landmarks, fuse, carry, track_intrs, self.sched.streams, lm_weight, lm_gate_px)
@@ -1101,6 +1267,12 @@ class StreamPool:
             if sorted(self.anchors) != list(range(self.sched.streams)):
                 raise ValueError(f"anchors must name every stream 0 .. {self.sched.streams - 1}, got "
                                  f"{sorted(self.anchors)}")
+        mkw = _check_motion(motion, self.fuse, motion_len, motion_min_frames, motion_iters, motion_horizon,
+                            motion_max_angle, motion_inverse_rotation)
+        self.motion = mkw is not None
+        self._motion = None
+        if self.motion:
+            self._motion = MotionTracker(window, stride, streams, **mkw)
         self._ratios = {}
         if self.fuse:
             self._fuse_key = self._anchor_key(self.anchors[0])
@@ -1143,6 +1315,8 @@ class StreamPool:
             self._carry.reset(stream)
         if self._lm is not None:
             self._lm.reset(stream)
+        if self._motion is not None:
+            self._motion.reset(stream)
         if stream is None:
             self._rings = self._wins = self._hw = self._dev = None
             self._tables = {}
@@ -1154,6 +1328,11 @@ class StreamPool:
     def landmark_map(self):
         """The LandmarkMap (landmarks=True), else None."""
         return self._lm
+
+    @property
+    def motion_tracker(self):
+        """The MotionTracker (motion=True), else None."""
+        return self._motion
 
     # -- rings ------------------------------------------------------------------------------------
     def _allocate(self, per):
@@ -1287,7 +1466,11 @@ class StreamPool:
         out = self._fused = self._fuser.fuse(enc, hops, w)
         self._fused_hops = list(hops)  # (the rows of `out`, for the PnP feedback of _landmarks)
         final = self._fuser.sched.final
-        return [(sid, r._replace(**_fused_fields(out, b, final))) for b, (sid, r) in enumerate(results)]
+        results = [(sid, r._replace(**_fused_fields(out, b, final))) for b, (sid, r) in enumerate(results)]
+        if self.motion:  # (on the rows of the fuse launch, in its order)
+            mo = self._motion.update(self._fused_hops, out)
+            results = [(sid, r.with_motion(mo, b)) for b, (sid, r) in enumerate(results)]
+        return results
 
     def _landmarks(self, order, results, co, later):
         """One comet_landmark_update launch for all the hops of a push, after _fuse: results and the

@@ -781,6 +781,74 @@ int comet_landmark_pnp(const float* tracks, const float* weights, const double* 
                        double fuse_cy, double* q_out, float* R_out, double* t_out, int32_t* n_in, float* rms_px,
                        int32_t* state_out, void* stream);
 
+/* comet_motion_fit (DESIGN.md "Motion estimate"): the frames at the positions [0, s) of a hop leave the
+ *   window with a final fused pose and are committed exactly once (the rule of comet_landmark_update), so
+ *   the committed poses of a stream are a time series in frames. This keeps a short history of them per
+ *   stream and fits a constant angular velocity and a constant linear velocity to its newest frames, in one
+ *   launch per push after that push's comet_pose_fuse: grid (n), one wave of 64 threads per hop, no LDS, no
+ *   atomics, no communication between workgroups. Everything is IEEE double evaluated as written (no
+ *   contraction); atan2, sin and cos are the device library's. It reports only: nothing is written but the
+ *   state and the outputs.
+ *   State: hist [S, cap, COMET_MOTION_ROW] f64, rows (q[4] w first, t[3], w), cap <= 64; hist_n [S] int32,
+ *     the frames committed. Frame number f of a stream (from 0) lives in row f % cap. The row of the stream of
+ *     hop h is stream_idx[h] (stream_idx_host: the same values on the host). hist_n saturates without losing
+ *     the row: a count c >= COMET_MOTION_COUNT_FOLD is stored as cap + c % cap; a negative count reads as 0.
+ *   Inputs per hop: R [n, T, 4] f32 quaternions (w first) and T [n, T, 3] f64, the fused_R / fused_T of that
+ *     push; weights [n, T] f32 or NULL (= 1); first [n] int32.
+ *   Per hop h, with c = first[h] ? 0 : hist_n:
+ *   1. Append: position i = 0 .. s - 1 becomes frame number c + i: q = R[h, i] widened to double, conjugated
+ *      when inverse_rotation = 1 (the convention of comet_landmark_update); t = T[h, i]; w = weights[h, i]. A
+ *      frame is always stored, so a row's age is its time offset; if q, t or w is not finite or w <= 0 it is
+ *      stored with w = 0 (q and t as they came). hist_n = c + s. Of more than cap frames the newest cap stay.
+ *   2. Fit over the newest m = min(hist_n, fit_len) rows: lane k holds the row of age k (k = 0: the newest
+ *      committed frame), tau_k = -k. A row is usable when k < m and w != 0 (this function stores w >= 0 only; a
+ *      NaN or negative w can only come from the caller's hist and is summed as it is). n_used = usable rows.
+ *   Sums: every lane contributes its term, or +0 when its row is not usable; the 64 values are combined by the
+ *     fixed tree p[l] += p[l + d], d = 32, 16, .., 1 (__shfl_down), and lane 0's value is used. With wt = w tau:
+ *     Sw = sum w, St = sum wt, Stt = sum wt tau, and for a component x: Sp = sum w x, Stp = sum wt x. Line:
+ *     D = Sw Stt - St St, slope = (Sw Stp - St Sp) / D, offset = (Sp - slope St) / Sw.
+ *   Rotation: q_ref = the newest usable row. `iters` passes: d_k = q_k (x) conj(q_ref) (Hamilton product),
+ *     negated when its w < 0; with nv = |v| = sqrt(x^2 + y^2 + z^2): theta = 2 atan2(nv, w), phi_k =
+ *     (theta / nv) v, and theta = 0, phi_k = 0 when nv == 0. A usable row with theta > max_angle: state 3. The
+ *     line through each component of phi gives omega (slope) and a (offset); q_ref <- Exp(a) (x) q_ref,
+ *     Exp(p) = (cos(|p| / 2), (sin(|p| / 2) / |p|) p), the identity when |p| == 0; then divided by its norm,
+ *     negated when its w < 0 (the fuser's sign rule). q0 = q_ref after the last pass. One more pass takes
+ *     phi_k against q0 (theta > max_angle: state 3 again) and the residual r_k = phi_k - omega tau_k (the offset
+ *     is in q0): rot_rms = sqrt(sum w |r_k|^2 / Sw).
+ *   Translation: the same line through each component of t gives vel (slope) and t0 (offset);
+ *     trans_rms[j] = sqrt(sum w ((t_j - t0_j) - vel_j tau)^2 / Sw).
+ *   Prediction at tau = 1 .. P, P = T - s + horizon, counted from the newest committed frame: pred_q =
+ *     Exp(omega tau) (x) q0, conjugated back when inverse_rotation = 1; pred_t = t0 + vel tau. The first T - s
+ *     of them are the window positions i = s .. T - 1 (tau = i - s + 1), for which the innovation against that
+ *     push's fused pose is reported too: innov_rot = theta of R[h, i] (x) conj(pred_q) as above, innov_trans =
+ *     |T[h, i] - pred_t|.
+ *   State int32, in this order: 0 n_used < min_frames | -1 Sw, St, Stt or D not finite | 2 D <= 0 | 3 a relative
+ *     rotation beyond max_angle | -1 an omega, a, q_ref, rms, vel or t0 that is not finite | 1 fitted. For every
+ *     state other than 1: omega = vel = 0, q0 / t0 = the newest committed row bit for bit, rot_rms, trans_rms
+ *     and the innovations are +inf, every prediction repeats the newest committed pose (R[h, s - 1] widened,
+ *     T[h, s - 1]). The history is updated in every state.
+ *   Outputs per hop: omega [3] f64 rad / frame with R(tau) = Exp(omega tau) R0 for the rotation as stored
+ *     (after the conjugation on load); q0 [4] f64 in that same convention; vel [3], t0 [3] f64; rot_rms f32;
+ *     trans_rms [3] f32; n_used, state int32; pred_q [P, 4], pred_t [P, 3] f64; innov_rot, innov_trans
+ *     [T - s] f32.
+ *   COMET_EINVAL before anything is launched, checked in this order: a null pointer (weights may be null),
+ *   n < 1, T < 2, s outside [1, T - 1], cap outside [2, 64], fit_len outside [2, cap], min_frames outside
+ *   [2, fit_len], iters outside [1, COMET_MOTION_MAX_ITERS], horizon outside [0, COMET_MOTION_MAX_HORIZON],
+ *   max_angle not in (0, pi), inverse_rotation not 0 or 1, a host stream index outside [0, S) or two equal
+ *   ones (two hops on one ring would race; a stream completes at most one hop per push), R / hist not 16-B
+ *   aligned or T / omega / q0 / vel / t0 / pred_q / pred_t not 8-B aligned. The kernel range-checks every row
+ *   index before it addresses memory. */
+#define COMET_MOTION_ROW 8
+#define COMET_MOTION_COUNT_FOLD (1 << 30)
+#define COMET_MOTION_MAX_ITERS 8
+#define COMET_MOTION_MAX_HORIZON 64
+int comet_motion_fit(const float* R, const double* T, const float* weights, const int32_t* first,
+                     const int32_t* stream_idx, const int32_t* stream_idx_host, double* hist, int32_t* hist_n,
+                     int S, int cap, int n, int Tw, int s, int fit_len, int min_frames, int iters, int horizon,
+                     double max_angle, int inverse_rotation, double* omega, double* q0, double* vel, double* t0,
+                     float* rot_rms, float* trans_rms, int32_t* n_used, int32_t* state, double* pred_q,
+                     double* pred_t, float* innov_rot, float* innov_trans, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Debug support (bounds asserts and a NaN / Inf check mode).
  * comet_count_nonfinite: adds the number of NaN / Inf elements of x (n elements, dtype) to

@@ -58,12 +58,17 @@ valid landmarks per hop and whether pred_pose_enc stayed identical. A report, no
 PoseStream(fuse=True, carry=True, landmarks=True) objects, pnp on (report only, pnp_weight 0) and off,
 alternate push by push in one process; ms per push of each, the comet_landmark_pnp launch of a hop alone
 (20 back-to-back launches / 20), the solved positions per hop and whether pred_pose_enc stayed identical.
-A report, not a pass criterion."""
+A report, not a pass criterion.
+--fuse --motion: the motion estimate (comet_motion_fit, DESIGN.md "Motion estimate"): two PoseStream(fuse=True)
+objects with fixed query points, motion on and off, alternate push by push in one process; ms per push of
+each, the comet_motion_fit launch of a hop alone (20 back-to-back launches / 20), the states seen and whether
+pred_pose_enc and the fused poses stayed identical. A report, not a pass criterion."""
 import argparse
 import json
 import os
 import statistics
 import sys
+from types import SimpleNamespace
 
 import torch
 
@@ -394,6 +399,60 @@ def pnp_bench(model, args, dev, cfg):
         flush=True)
 
 
+def motion_bench(model, args, dev):
+    """--motion (with --fuse): ms per push of PoseStream(fuse) with motion on against off, the two objects
+    alternating push by push in one process, and the comet_motion_fit launch alone on the hop's own fused
+    poses (a scratch tracker: the stream's history is left alone)."""
+    from comet_amd.stream import Hop, MotionTracker, PoseStream
+    T, S, N = args.frames, args.image, args.tracks
+    g = torch.Generator(device=dev).manual_seed(1)
+    total = T + args.warmup + args.hops - 1
+    frames = torch.randn(total, 3, S, S, device=dev, generator=g)
+    q = torch.rand(N, 2, device=dev, generator=g) * (S - 1)
+    R0 = torch.tensor([0.8, 0.2, -0.4, 0.4], device=dev)
+    anchor = (R0 / R0.norm(), torch.tensor([331.25, 247.5, 11.375], device=dev), 268.44, 0.5, "AMD")
+    kw = dict(window=T, stride=1, precision=torch.bfloat16, anchor=anchor, fuse=True)
+    objs = {True: PoseStream(model, motion=True, **kw), False: PoseStream(model, **kw)}
+    scratch = MotionTracker(T, 1, 1)
+    for o in objs.values():
+        assert o.push(frames[:T - 1], query_points=q) == []
+    ta, tb, tc, states, same = [], [], [], {}, True
+    for j in range(args.warmup + args.hops):
+        i = j + T - 1
+        order = (True, False) if j % 2 == 0 else (False, True)  # (neither path always runs first)
+        ms, res = {}, {}
+        for f in order:
+            ms[f], res[f] = _timed(lambda: objs[f].push(frames[i], query_points=q))
+        r, off = res[True][0], res[False][0]
+        fused = SimpleNamespace(R=r.fused_R.contiguous(), T=r.fused_T.contiguous())
+
+        def alone():
+            for _ in range(GATHER_REPS):  # (reset: the same hop again is a first hop again)
+                scratch.reset()
+                scratch.update([(0, Hop(r.frame_index, 0))], fused)
+        ms_c, _ = _timed(alone)
+        if j >= args.warmup:
+            ta.append(ms[True])
+            tb.append(ms[False])
+            tc.append(ms_c / GATHER_REPS)
+            st = int(r.motion_state)
+            states[st] = states.get(st, 0) + 1
+            same = same and torch.equal(r.pred_pose_enc, off.pred_pose_enc) and torch.equal(r.fused_R, off.fused_R) \
+                and torch.equal(r.fused_T, off.fused_T)
+    a, b, c = statistics.median(ta), statistics.median(tb), statistics.median(tc)
+    print(json.dumps({
+        "metric": f"ms per push, motion on against off, PoseStream fuse, T={T} {S}^2 N={N}, bf16, stride 1",
+        "motion_on_ms": round(a, 3), "motion_off_ms": round(b, 3), "on_over_off": round(a / b, 4),
+        "min_motion_on_ms": round(min(ta), 3), "min_motion_off_ms": round(min(tb), 3),
+        "motion_fit_ms": round(c, 4), "min_motion_fit_ms": round(min(tc), 4),
+        "motion_fit_timing": f"device events around {GATHER_REPS} back-to-back launches / {GATHER_REPS}, median over the "
+                             "pushes (a first hop each: one frame in the history)",
+        "motion_len": 16, "motion_iters": 2, "states_seen": {str(k): v for k, v in sorted(states.items())},
+        "pose_enc_and_fused_poses_identical_on_vs_off": same, "pushes": args.hops, "warmup": args.warmup,
+        "data": "synthetic (N(0,1) frames, U[0,S-1] query points); random-init weights: the poses carry no motion"}),
+        flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16, help="window length T")
@@ -418,6 +477,8 @@ def main():
     ap.add_argument("--pnp", action="store_true",
                     help="--fuse --carry --landmarks: time the PnP refinement (comet_landmark_pnp) on against off")
     ap.add_argument("--pnp-huber-px", type=float, default=3.0, help="--pnp: pnp_huber_px (not a recommendation)")
+    ap.add_argument("--motion", action="store_true",
+                    help="--fuse: time the motion estimate (comet_motion_fit) on against off")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         print("stream_bench: no GPU", file=sys.stderr)
@@ -431,6 +492,11 @@ def main():
     cfg = load_config()
     torch.manual_seed(0)
     model = instantiate(cfg.MODEL, _recursive_=False, cfg=cfg).to(dev).eval()
+    if args.motion:
+        if not args.fuse or args.carry or args.streams is not None:
+            ap.error("--motion needs --fuse, without --carry and --streams")
+        motion_bench(model, args, dev)
+        return 0
     if args.warm and not args.carry:
         ap.error("--warm needs --carry")
     if args.landmarks:
