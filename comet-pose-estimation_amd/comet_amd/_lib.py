@@ -95,6 +95,7 @@ RING_MAX_TENSORS = 4  # COMET_RING_MAX_TENSORS
 FUSE_ROW = 20         # COMET_FUSE_ROW: doubles per accumulator row of comet_pose_fuse
 CARRY_MAX_TRACKS, CARRY_MAX_CANDIDATES, CARRY_MAX_CELLS = 4096, 65536, 8192  # COMET_CARRY_MAX_*
 LM_ROW = 12           # COMET_LM_ROW: doubles per accumulator row of comet_landmark_update
+LM_ARCH_ROW, LM_ARCH_MAX = 20, 4096  # COMET_LM_ARCH_*: doubles per archive entry, entries per stream (comet_landmark_reid)
 PNP_MAX_ITERS = 16    # COMET_PNP_MAX_ITERS: Gauss-Newton steps of comet_landmark_pnp
 MOTION_ROW = 8        # COMET_MOTION_ROW: doubles per history row of comet_motion_fit
 MOTION_MAX_CAP, MOTION_MAX_ITERS, MOTION_MAX_HORIZON = 64, 8, 64  # the wave width, COMET_MOTION_MAX_*
@@ -205,6 +206,8 @@ SIGNATURES = {
                                   ctypes.c_double, _INT, ctypes.c_double, c_vp, _INT, c_vp, c_vp, ctypes.c_double,
                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp,
                                   c_vp, c_vp, c_vp, c_vp]),
+    "comet_landmark_reid": (_INT, [c_vp] * 12 + [_INT] + [c_vp] * 3 + [_INT, c_vp] + [_INT] * 6 +
+                            [ctypes.c_double] * 3 + [c_vp] * 6),
     "comet_motion_fit": (_INT, [c_vp] * 8 + [_INT] * 9 + [ctypes.c_double, _INT] + [c_vp] * 13),
 }
 

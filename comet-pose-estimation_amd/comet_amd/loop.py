@@ -666,18 +666,36 @@ def _carry_fields(carry):
 LANDMARK_FIELDS = ("track_id", "x", "y", "z", "n_obs")
 
 
+def _stream_archive(cfg):
+    """cfg.stream.lm_archive (default 0: off) / reid_px (required with lm_archive: nothing here derives one) /
+    reid_min_cos (0.5, a stated value, not a tuned one) / lm_arch_min_obs (null: lm_min_obs) -> the archive
+    keywords of PoseStream / StreamPool ({} with the archive off)."""
+    cap = int(_get(cfg, "stream.lm_archive", 0))
+    if not cap:
+        return {}
+    px = _get(cfg, "stream.reid_px", None)
+    if px is None:
+        raise ValueError("cfg.stream.lm_archive needs cfg.stream.reid_px, the re-identification gate in pixels")
+    obs = _get(cfg, "stream.lm_arch_min_obs", None)
+    return dict(lm_archive=cap, reid_px=float(px), reid_min_cos=float(_get(cfg, "stream.reid_min_cos", 0.5)),
+                lm_arch_min_obs=None if obs is None else int(obs))
+
+
 def _stream_landmarks(cfg, fuse, carry):
     """cfg.stream.landmarks (default false) / lm_min_obs (3) / lm_min_pivot (1e-8, a guard, not a tuned
     value) / lm_weight (null or "score") / lm_gate_px (null: no gate) / lm_inverse_rotation (0) -> the
     landmark keywords of PoseStream / StreamPool without the intrinsics ({} with landmarks off), which
     depend on the sequence's box (_track_intr). fuse, carry: what _stream_fuse / _stream_carry returned."""
     if not _get(cfg, "stream.landmarks", False):
+        if int(_get(cfg, "stream.lm_archive", 0)):
+            raise ValueError("cfg.stream.lm_archive needs cfg.stream.landmarks: the archive keeps the landmarks of dead "
+                             "tracks")
         return {}
     if not fuse or not carry:
         raise ValueError("cfg.stream.landmarks needs cfg.stream.fuse and cfg.stream.carry: a landmark is a carried "
                          "track triangulated from the fused poses")
     gate = _get(cfg, "stream.lm_gate_px", None)
-    return dict(landmarks=True, lm_min_obs=int(_get(cfg, "stream.lm_min_obs", 3)),
+    return dict(_stream_archive(cfg), landmarks=True, lm_min_obs=int(_get(cfg, "stream.lm_min_obs", 3)),
                 lm_min_pivot=float(_get(cfg, "stream.lm_min_pivot", 1e-8)), lm_weight=_get(cfg, "stream.lm_weight", None),
                 lm_gate_px=None if gate is None else float(gate),
                 lm_inverse_rotation=int(_get(cfg, "stream.lm_inverse_rotation", 0)))
@@ -781,6 +799,24 @@ def _log_landmarks(csv_path, lm, stream=0):
     return len(rows)
 
 
+def archive_csv(csv_path):
+    """The path of the archive CSV that goes with the hop CSV csv_path: <stem>_archive.csv."""
+    stem, ext = os.path.splitext(csv_path)
+    return stem + "_archive" + ext
+
+
+def _log_archive(csv_path, lm, stream=0):
+    """LandmarkMap.archive_snapshot(stream), the landmarks of dead tracks the stream's archive holds, as
+    archive_csv(csv_path): one row per entry in use, with the landmark CSV's fields (id = the landmark's
+    identity), the header alone when there is none. -> number of rows."""
+    logger = CsvLogger(archive_csv(csv_path), LANDMARK_FIELDS)
+    ids, X, n_obs = lm.archive_snapshot(stream)
+    rows = torch.cat([ids.double()[:, None], X.double(), n_obs.double()[:, None]], 1).tolist()
+    for i, x, y, z, k in rows:
+        logger.log(dict(zip(LANDMARK_FIELDS, (int(i), x, y, z, int(k)))))
+    return len(rows)
+
+
 def _carry_counts(r):
     """(survivors, born, padded) of a carried StreamResult, from track_src (ops.CarryOut)."""
     src = r.track_src.tolist()
@@ -848,7 +884,10 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
     lm_gate_px and lm_inverse_rotation) turns the landmark map on (PoseStream landmarks=True) with the
     intrinsics of the anchor's dataset mapped into `box` (data.crop_intrinsics); the hop CSV is what it
     was, and at the end of the stream landmarks_csv(csv_path) takes the final snapshot, one row per valid
-    live landmark (LANDMARK_FIELDS).
+    live landmark (LANDMARK_FIELDS). cfg.stream.lm_archive = C > 0 (with reid_px, required, reid_min_cos and
+    lm_arch_min_obs) turns the landmark archive on (PoseStream lm_archive): archive_csv(csv_path) then takes
+    LandmarkMap.archive_snapshot at the end, with the same fields; with it off (the default) the hop CSV and
+    the landmark CSV are what they were and no archive CSV is written.
     cfg.stream.motion (default false; needs fuse; with motion_len, motion_min_frames, motion_iters,
     motion_horizon, motion_max_angle and motion_inverse_rotation) turns the motion estimate on (PoseStream
     motion=True); the hop CSV is what it was, and motion_csv(csv_path) takes one row per hop (MOTION_FIELDS)."""
@@ -899,6 +938,8 @@ def stream_eval(model, frames_iter, cfg, box, csv_path, sp=None, sift=None, quer
         _log_hop(logger, fields, last[0], window, None, last=last[1])
     if lm:
         _log_landmarks(csv_path, stream.landmark_map)
+        if lm.get("lm_archive"):
+            _log_archive(csv_path, stream.landmark_map)
     return hops
 
 
@@ -985,6 +1026,8 @@ def stream_eval_pool(model, sequences, cfg, csv_dir, sp=None, sift=None, query_p
                 _log_hop(running[sid][3], fields, r, window, None, last=row)
             if lm:
                 _log_landmarks(running[sid][3].path, pool.landmark_map, sid)
+                if lm.get("lm_archive"):
+                    _log_archive(running[sid][3].path, pool.landmark_map, sid)
             del running[sid]
 
     while True:

@@ -850,6 +850,69 @@ def landmark_update(tracks, R, T, ids, src, stream_idx, stream_idx_host, intr, i
     return out
 
 
+class ReidOut(NamedTuple):
+    src_lm: torch.Tensor      # [n, N] int32: src, with j for the matched slots (what ops.landmark_update then takes)
+    lm_id: torch.Tensor       # [n, N] int32 landmark identity: the archived id of a restored row, else ids (-1: a pad)
+    reid_state: torch.Tensor  # [n, N] int32: 0 not born, 1 matched, 2 no candidate in the gate, 3 its pick took another slot
+    reid_dist: torch.Tensor   # [n, N] f32 pixel distance of a match (+inf where reid_state != 1)
+    stats: torch.Tensor       # [n, 4] int32 (retired, matched, entries in use afterwards, retirements that overwrote)
+
+
+def landmark_reid(tracks, R, T, ids, src, stream_idx, stream_idx_host, intr, intr_host, acc, acc_id, alias, arch,
+                  arch_id, arch_cursor, ws, reid_px, reid_min_cos=0.5, arch_min_obs=3, inverse_rotation=0,
+                  min_pivot=1e-8):
+    """comet_landmark_reid (include/comet_hip.h): before ops.landmark_update of the same push, the rows of the
+    tracks that died on these n hops are retired to the archive arch [S * C, 20] f64 / arch_id [S * C] int32 /
+    arch_cursor [S] int32, and the tracks born on the projection of an archived landmark get its row (acc
+    [rows, 12] f64, acc_id, alias [rows] int32, all in place) -> ReidOut, one launch. tracks, R, T, ids, src,
+    stream_idx, intr and their host copies as for ops.landmark_update; ws [>= n, N, 12] f64 is a workspace.
+    reid_min_cos = 0.5 is a stated value, not a tuned one."""
+    _req_cuda(tracks, R, T, ids, src, stream_idx, intr, acc, acc_id, alias, arch, arch_id, arch_cursor, ws)
+    if tracks.dim() != 4 or tracks.shape[3] != 2 or tracks.dtype != torch.float32 or not tracks.is_contiguous():
+        raise L.CometHipError(f"landmark_reid: tracks must be a dense f32 [n, T, N, 2] tensor, got "
+                              f"{tuple(tracks.shape)} {tracks.dtype}")
+    n, Tw, N = tracks.shape[:3]
+    for name, t, shape, dtype in (("R", R, (n, Tw, 4), torch.float32), ("T", T, (n, Tw, 3), torch.float64),
+                                  ("ids", ids, (n, N), torch.int32), ("src", src, (n, N), torch.int32),
+                                  ("stream_idx", stream_idx, (n,), torch.int32), ("intr", intr, (n, 4), torch.float64)):
+        if t.shape != shape or t.dtype != dtype or not t.is_contiguous():
+            raise L.CometHipError(f"landmark_reid: {name} must be a dense {dtype} {list(shape)} tensor")
+    if acc.dim() != 2 or acc.shape[1] != L.LM_ROW or acc.dtype != torch.float64 or not acc.is_contiguous():
+        raise L.CometHipError(f"landmark_reid: acc must be a dense f64 [rows, {L.LM_ROW}] tensor")
+    if arch.dim() != 2 or arch.shape[1] != L.LM_ARCH_ROW or arch.dtype != torch.float64 or not arch.is_contiguous():
+        raise L.CometHipError(f"landmark_reid: arch must be a dense f64 [entries, {L.LM_ARCH_ROW}] tensor")
+    S = arch_cursor.numel()
+    if S < 1 or arch.shape[0] % S != 0:
+        raise L.CometHipError("landmark_reid: arch needs S * C entries for the S streams of arch_cursor")
+    C = arch.shape[0] // S
+    for name, t, count in (("acc_id", acc_id, acc.shape[0]), ("alias", alias, acc.shape[0]),
+                           ("arch_id", arch_id, arch.shape[0]), ("arch_cursor", arch_cursor, S)):
+        if t.shape != (count,) or t.dtype != torch.int32 or not t.is_contiguous():
+            raise L.CometHipError(f"landmark_reid: {name} must be a dense int32 [{count}] tensor")
+    if acc.shape[0] < S * N:
+        raise L.CometHipError(f"landmark_reid: acc needs {S} * {N} rows for the streams of arch_cursor")
+    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() < n * N * L.LM_ROW:
+        raise L.CometHipError(f"landmark_reid: ws must be a dense f64 tensor of at least n * N * {L.LM_ROW} values")
+    if len(stream_idx_host) != n or len(intr_host) != 4 * n:
+        raise L.CometHipError("landmark_reid: stream_idx_host needs n entries and intr_host 4 n")
+    dev = tracks.device
+    if any(t.device != dev for t in (R, T, ids, src, stream_idx, intr, acc, acc_id, alias, arch, arch_id, arch_cursor, ws)):
+        raise L.CometHipError("landmark_reid: every tensor must be on one device")
+    i32 = dict(device=dev, dtype=torch.int32)
+    out = ReidOut(torch.empty(n, N, **i32), torch.empty(n, N, **i32), torch.empty(n, N, **i32),
+                  torch.empty(n, N, device=dev), torch.empty(n, 4, **i32))
+    e0 = PROF.start()
+    L.check(L.load().comet_landmark_reid(_p(tracks), _p(R), _p(T), _p(ids), _p(src), _p(stream_idx),
+                                         ctypes.addressof(stream_idx_host), _p(intr), ctypes.addressof(intr_host),
+                                         _p(acc), _p(acc_id), _p(alias), S * N, _p(arch), _p(arch_id), _p(arch_cursor),
+                                         arch.shape[0], _p(ws), n, Tw, N, C, int(inverse_rotation), int(arch_min_obs),
+                                         float(min_pivot), float(reid_px), float(reid_min_cos), *[_p(t) for t in out],
+                                         stream()), "landmark_reid")
+    if e0 is not None:
+        PROF.stop(e0, "comet_landmark_reid", 0.0, float(n * (C * 8 * (L.LM_ARCH_ROW + 1) + N * (8 * L.LM_ROW + 40))))
+    return out
+
+
 class PnpOut(NamedTuple):
     q: torch.Tensor       # [n, T, 4] f64 refined rotation (unit quaternion, w >= 0; the input where state != 1)
     R: torch.Tensor       # [n, T, 4] f32, q rounded (the input bit for bit where state != 1)

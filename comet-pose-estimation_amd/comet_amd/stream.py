@@ -138,6 +138,10 @@ class StreamResult(_StreamFields):
     motion_pred_T = None     # [T - stride + horizon, 3] float64
     motion_innov_rot = None    # [T - stride] f32 rad: fused against predicted, positions [stride, T)
     motion_innov_trans = None  # [T - stride] f32
+    # lm_archive > 0 only (LandmarkMap.reidentify; attributes too)
+    landmark_ids = None  # [N] int32 landmark identity: the archived id of a restored landmark, else track_ids
+    reid_state = None    # [N] int32: 0 not born, 1 matched to the archive, 2 no candidate, 3 its pick took another slot
+    reid_dist = None     # [N] f32 pixel distance of a match (+inf where reid_state != 1)
 
     def _replace(self, **kw):
         r = super()._replace(**kw)
@@ -153,6 +157,12 @@ class StreamResult(_StreamFields):
         """The result with row b of an ops.LandmarkOut."""
         r = self._replace()
         r.landmarks, r.landmark_obs, r.landmark_err, r.landmark_state = lo.X[b], lo.n_obs[b], lo.err_px[b], lo.state[b]
+        return r
+
+    def with_reid(self, ro, b):
+        """The result with row b of an ops.ReidOut."""
+        r = self._replace()
+        r.landmark_ids, r.reid_state, r.reid_dist = ro.lm_id[b], ro.reid_state[b], ro.reid_dist[b]
         return r
 
     def with_pnp(self, po, b):
@@ -646,7 +656,8 @@ def gate_scores(score, state, err_px, s, gate_px):
 def _landmark_step(lm, sids, tr, sc, fo, ids, src, lm_weight, lm_gate_px, pnp=None, fuser=None, hops=None):
     """The landmark launch of a push: the hops of `sids` with pred_tracks tr [n, T, N, 2], pred_score sc
     [n, T, N], their ops.FuseOut rows fo and the carry's ids / src [n, N] -> (ops.LandmarkOut, the score
-    TrackCarry.update takes: sc itself, or its gated copy when lm_gate_px is given, the ops.PnpOut or None).
+    TrackCarry.update takes: sc itself, or its gated copy when lm_gate_px is given, the ops.PnpOut or None, the
+    ops.ReidOut of the archive launch that precedes the landmark launch, or None with the archive off).
     pnp (_check_pnp): the PnP launch follows on the same rows, with the landmark launch's weights; with
     pnp["weight"] > 0 it adds its poses to the accumulator of `fuser`, on the rows of `hops` = [(stream, Hop)],
     the hops fo was fused from, in its order."""
@@ -655,6 +666,10 @@ def _landmark_step(lm, sids, tr, sc, fo, ids, src, lm_weight, lm_gate_px, pnp=No
     n, T = tr.shape[:2]
     w = sc.float().contiguous() if lm_weight == "score" else None
     trf, R, Tx = tr.float().contiguous(), fo.R.view(n, T, 4), fo.T.view(n, T, 3)
+    ro = None
+    if lm.archive:  # dying rows retire, born slots on an archived landmark get its row back: update() then adds
+        ro = lm.reidentify(sids, trf, R, Tx, ids, src)
+        src = ro.src_lm
     lo = lm.update(sids, trf, R, Tx, ids, src, w)
     po = None
     if pnp is not None:
@@ -662,7 +677,25 @@ def _landmark_step(lm, sids, tr, sc, fo, ids, src, lm_weight, lm_gate_px, pnp=No
                     huber_px=pnp["huber_px"], min_pts=pnp["min_pts"], weight=pnp["weight"])
     if lm_gate_px is not None:
         sc = gate_scores(sc, lo.state, lo.err_px, lm.stride, lm_gate_px)
-    return lo, sc, po
+    return lo, sc, po, ro
+
+
+def _check_archive(archive, reid_px, reid_min_cos, arch_min_obs, min_obs):
+    """-> (capacity, reid_px, reid_min_cos, arch_min_obs) of a LandmarkMap; capacity 0: the archive is off."""
+    archive = int(archive)
+    if not 0 <= archive <= L.LM_ARCH_MAX:
+        raise ValueError(f"archive must be 0 (off) or a capacity of 1 to {L.LM_ARCH_MAX} entries per stream, got {archive}")
+    if not archive:
+        return 0, None, float(reid_min_cos), int(min_obs if arch_min_obs is None else arch_min_obs)
+    if reid_px is None or not 0.0 < float(reid_px) < float("inf"):
+        raise ValueError(f"archive > 0 needs reid_px, a finite distance in pixels > 0 (nothing here derives one), got "
+                         f"{reid_px}")
+    if not -1.0 <= float(reid_min_cos) <= 1.0:
+        raise ValueError(f"reid_min_cos must lie in [-1, 1], got {reid_min_cos}")
+    arch_min_obs = int(min_obs if arch_min_obs is None else arch_min_obs)
+    if arch_min_obs < 2:
+        raise ValueError(f"arch_min_obs must be at least 2, got {arch_min_obs}")
+    return archive, float(reid_px), float(reid_min_cos), arch_min_obs
 
 
 class LandmarkMap:
@@ -685,13 +718,18 @@ class LandmarkMap:
     min_pivot = 1e-8 is a guard against dividing by a rounding residue, not a tuned value: a pivot of the
     LDL^T at or below min_pivot * max(diag M) marks the slot ill-conditioned (no parallax yet).
     inverse_rotation = 0: x_cam = R(q) X + T, the way the dataset labels are produced and consumed
-    (DESIGN.md "Landmarks"); 1 uses the transpose. A landmark lives as long as its slot carries its
-    track; nothing is kept after the track dies."""
+    (DESIGN.md "Landmarks"); 1 uses the transpose. With archive = 0 a landmark lives as long as its slot
+    carries its track and nothing is kept after the track dies. With archive = C > 0 (DESIGN.md "Landmark
+    archive") the row of a dying track is kept in a ring of C entries per stream, and reidentify(), one
+    comet_landmark_reid launch before update(), hands it back with its identity to a track born within reid_px
+    pixels of its projection (required: nothing here derives one) while it still faces the camera
+    (reid_min_cos = 0.5 is a stated value, not a tuned one); arch_min_obs (None: min_obs) frames make a row
+    worth keeping."""
 
     _TABLES_MAX = 1024
 
     def __init__(self, window, stride=1, streams=1, tracks=512, intrs=None, min_obs=3, min_pivot=1e-8,
-                 inverse_rotation=0):
+                 inverse_rotation=0, archive=0, reid_px=None, reid_min_cos=0.5, arch_min_obs=None):
         if stride < 1 or stride >= window:
             raise ValueError(f"landmarks need 1 <= stride < window (stride {stride}, window {window})")
         if streams < 1 or not 1 <= int(tracks) <= L.CARRY_MAX_TRACKS:
@@ -703,6 +741,8 @@ class LandmarkMap:
         self.window, self.stride, self.streams, self.tracks = int(window), int(stride), int(streams), int(tracks)
         self.intrs = [tuple(float(v) for v in i) for i in intrs]
         self.min_obs, self.min_pivot, self.inverse_rotation = int(min_obs), float(min_pivot), int(bool(inverse_rotation))
+        self.archive, self.reid_px, self.reid_min_cos, self.arch_min_obs = _check_archive(
+            archive, reid_px, reid_min_cos, arch_min_obs, self.min_obs)
         self.device = None
         self._last = {}  # stream -> (LandmarkOut, row, ids [n, N])
 
@@ -719,6 +759,14 @@ class LandmarkMap:
         self.acc = torch.zeros(self.streams * self.tracks, L.LM_ROW, dtype=torch.float64, device=dev)
         self.acc_id = torch.full((self.streams * self.tracks,), -1, dtype=torch.int32, device=dev)
         self._tables, self._last = {}, {}
+        if self.archive:
+            i32 = dict(dtype=torch.int32, device=dev)
+            self.arch = torch.zeros(self.streams * self.archive, L.LM_ARCH_ROW, dtype=torch.float64, device=dev)
+            self.arch_id = torch.full((self.streams * self.archive,), -1, **i32)
+            self.arch_cursor = torch.zeros(self.streams, **i32)
+            self.alias = torch.full((self.streams * self.tracks,), -1, **i32)
+            self._ws = torch.empty(self.streams, self.tracks, L.LM_ROW, dtype=torch.float64, device=dev)
+            self._pending = None  # (sids, lm_id [n, N]) of a reidentify() whose update() has not come yet
 
     def _table(self, sids):
         hit = self._tables.get(sids)
@@ -745,7 +793,8 @@ class LandmarkMap:
 
     def reset(self, stream=None):
         """The rows of `stream` (default: of every stream) hold no landmark any more. A stream's first
-        hop has only births and pads, which overwrite their rows, so nothing else is cleared."""
+        hop has only births and pads, which overwrite their rows, so nothing else is cleared. With the
+        archive on, the stream's entries, cursor and aliases are freed too."""
         if stream is not None:
             self._id(stream)
         if self.device is None:
@@ -753,9 +802,49 @@ class LandmarkMap:
         if stream is None:
             self._last.clear()
             self.acc_id.fill_(-1)
+            if self.archive:
+                self._pending = None
+                self.arch_id.fill_(-1)
+                self.arch_cursor.zero_()
+                self.alias.fill_(-1)
         else:
-            self._last.pop(int(stream), None)
-            self.acc_id[int(stream) * self.tracks:(int(stream) + 1) * self.tracks] = -1
+            s = int(stream)
+            self._last.pop(s, None)
+            self.acc_id[s * self.tracks:(s + 1) * self.tracks] = -1
+            if self.archive:
+                self.arch_id[s * self.archive:(s + 1) * self.archive] = -1
+                self.arch_cursor[s:s + 1] = 0
+                self.alias[s * self.tracks:(s + 1) * self.tracks] = -1
+
+    def reidentify(self, sids, tracks, R, T, ids, src):
+        """The archive step of the hops of the streams `sids` (distinct), before update() on the same hops
+        and arguments: the rows update() is about to overwrite or clear are retired to the archive, and the
+        born slots are matched against it -> ops.ReidOut; hand its src_lm to update() in place of src."""
+        if not self.archive:
+            raise RuntimeError("reidentify needs a LandmarkMap with archive > 0")
+        sids = tuple(self._id(s) for s in sids)
+        if len(sids) == 0 or len(set(sids)) != len(sids):
+            raise ValueError(f"reidentify takes at least one hop and one hop per stream, got the streams {list(sids)}")
+        self._ensure(tracks.device)
+        idx, idx_host, intr, intr_host = self._table(sids)
+        out = ops.landmark_reid(tracks, R, T, ids, src, idx, idx_host, intr, intr_host, self.acc, self.acc_id,
+                                self.alias, self.arch, self.arch_id, self.arch_cursor, self._ws, self.reid_px,
+                                self.reid_min_cos, self.arch_min_obs, self.inverse_rotation, self.min_pivot)
+        self._pending = (sids, out.lm_id)
+        return out
+
+    def archive_snapshot(self, stream=0):
+        """(ids [A] int32, X [A, 3] float64, n_obs [A] int32) of the stream's archive entries in use, in
+        entry order (empty with the archive off, before the first hop and after a reset)."""
+        s = self._id(stream)
+        if not self.archive or self.device is None:
+            dev = self.device if self.device is not None else "cpu"
+            return (torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, 3, dtype=torch.float64, device=dev),
+                    torch.empty(0, dtype=torch.int32, device=dev))
+        sl = slice(s * self.archive, (s + 1) * self.archive)
+        on = self.arch_id[sl] >= 0
+        a = self.arch[sl][on]
+        return self.arch_id[sl][on], a[:, 12:15].contiguous(), a[:, 10].to(torch.int32)
 
     def update(self, sids, tracks, R, T, ids, src, weights=None):
         """The hops of the streams `sids` (distinct), in their order: tracks [n, T, N, 2] f32, R [n, T, 4]
@@ -767,6 +856,10 @@ class LandmarkMap:
         idx, idx_host, intr, intr_host = self._table(sids)
         out = ops.landmark_update(tracks, R, T, ids, src, idx, idx_host, intr, intr_host, self.acc, self.acc_id,
                                   self.stride, weights, self.inverse_rotation, self.min_obs, self.min_pivot)
+        if self.archive:  # the identities of these rows: the lm_id of the reidentify() of the same hops, if there was one
+            pending, self._pending = self._pending, None
+            if pending is not None and pending[0] == sids:
+                ids = pending[1]
         for b, s in enumerate(sids):
             self._last[s] = (out, b, ids)
         return out
@@ -802,7 +895,9 @@ class LandmarkMap:
 
     def snapshot(self, stream=0):
         """(ids [L] int32, X [L, 3] float64, n_obs [L] int32) of the stream's valid live landmarks, as its
-        last hop left them (empty before the first hop and after a reset)."""
+        last hop left them (empty before the first hop and after a reset). With the archive on the ids are
+        the landmark identities (ReidOut.lm_id) of the reidentify() that preceded that update() on the same
+        hops; an update() that no reidentify() of the same hops preceded reports the carry's ids."""
         last = self._last.get(self._id(stream))
         if last is None:
             dev = self.device if self.device is not None else "cpu"
@@ -1009,6 +1104,16 @@ class PoseStream:
     dies at the next hop by the carry's own score test. Landmark accuracy on real imagery and the effect
     of the gate on pose accuracy are unmeasured. With landmarks=False nothing changes.
 
+    lm_archive = C > 0 (needs landmarks=True and reid_px, a gate in pixels that nothing here derives) keeps the
+    landmark of a track that dies in a ring of C entries and gives it back, with its identity and its
+    observations, to a track born within reid_px of its projection while it still faces the camera (DESIGN.md
+    "Landmark archive"): one comet_landmark_reid launch per hop, before the landmark launch. reid_min_cos =
+    0.5 is a stated value, not a tuned one; lm_arch_min_obs (None: lm_min_obs) frames make a landmark worth
+    keeping. Results then carry landmark_ids (the landmark's identity, stable across re-identifications),
+    reid_state and reid_dist; stream.landmark_map.archive_snapshot() gives the archived landmarks. The accuracy
+    of re-identification on real imagery, every default, and whether archived landmarks improve pose drift are
+    unmeasured. With lm_archive=0 nothing changes.
+
     pnp=True (needs landmarks=True and pnp_huber_px, a Huber threshold in pixels that nothing here derives)
     poses every frame of the window against the landmark map (LandmarkMap.pnp, DESIGN.md "PnP refinement"):
     one comet_landmark_pnp launch per hop, after the landmark launch, runs pnp_iters Gauss-Newton steps from
@@ -1045,7 +1150,8 @@ class PoseStream:
                  warm_iters=None, landmarks=False, track_intr=None, lm_min_obs=3, lm_min_pivot=1e-8, lm_weight=None,
                  lm_gate_px=None, lm_inverse_rotation=0, pnp=False, pnp_iters=4, pnp_huber_px=None, pnp_min_pts=6,
                  pnp_weight=0.0, motion=False, motion_len=16, motion_min_frames=3, motion_iters=2, motion_horizon=1,
-                 motion_max_angle=2.0, motion_inverse_rotation=0):
+                 motion_max_angle=2.0, motion_inverse_rotation=0, lm_archive=0, reid_px=None, reid_min_cos=0.5,
+                 lm_arch_min_obs=None):
         self._pool = StreamPool(
             model, 1, window, stride, capacity, query_fn, None if anchor is None else [anchor], precision, fuse=fuse,
             fuse_weight=fuse_weight, carry=carry, carry_tracks=carry_tracks, carry_cell=carry_cell,
@@ -1056,7 +1162,8 @@ class PoseStream:
             lm_inverse_rotation=lm_inverse_rotation, pnp=pnp, pnp_iters=pnp_iters, pnp_huber_px=pnp_huber_px,
             pnp_min_pts=pnp_min_pts, pnp_weight=pnp_weight, motion=motion, motion_len=motion_len,
             motion_min_frames=motion_min_frames, motion_iters=motion_iters, motion_horizon=motion_horizon,
-            motion_max_angle=motion_max_angle, motion_inverse_rotation=motion_inverse_rotation)
+            motion_max_angle=motion_max_angle, motion_inverse_rotation=motion_inverse_rotation, lm_archive=lm_archive,
+            reid_px=reid_px, reid_min_cos=reid_min_cos, lm_arch_min_obs=lm_arch_min_obs)
         self.sched = self._pool.sched.scheds[0]  # the stream's own RingSchedule
         self.anchor = None if anchor is None else self._pool.anchors[0]
         self._hw = None  # the frame size push() holds the stream to
@@ -1064,7 +1171,7 @@ class PoseStream:
     # what a caller reads off a stream is the pool's (landmark_map: the LandmarkMap, motion_tracker: the
     # MotionTracker, or None)
     _POOLED = frozenset(("model", "query_fn", "precision", "fuse", "fuse_weight", "carry", "candidate_fn", "mask_fn",
-                         "warm", "warm_mode", "warm_iters", "landmarks", "lm_weight", "lm_gate_px", "pnp", "landmark_map",
+                         "warm", "warm_mode", "warm_iters", "landmarks", "lm_weight", "lm_gate_px", "lm_archive", "pnp", "landmark_map",
                          "_pnp", "_carry", "_lm", "_fuser", "_rings", "_wins", "motion", "motion_tracker", "_motion"))
 
     def __getattr__(self, name):
@@ -1218,6 +1325,8 @@ class StreamPool:
     comet_landmark_update launch, after the fuse launch, serves all the hops due in a push (the rows of two
     warm-start calls are stacked first); reset(stream) forgets that stream's landmarks. pnp / pnp_*: as
     PoseStream's; one comet_landmark_pnp launch per push, on the rows of the landmark launch in its order.
+    lm_archive / reid_px / reid_min_cos / lm_arch_min_obs: as PoseStream's; one comet_landmark_reid launch per
+    push, before the landmark launch, on its rows in its order; reset(stream) frees that stream's archive.
     motion / motion_*: as PoseStream's; one comet_motion_fit launch per push, on the rows of the fuse launch in
     its order; reset(stream) forgets that stream's history.
 
@@ -1232,7 +1341,8 @@ class StreamPool:
                  warm_iters=None, landmarks=False, track_intrs=None, lm_min_obs=3, lm_min_pivot=1e-8, lm_weight=None,
                  lm_gate_px=None, lm_inverse_rotation=0, pnp=False, pnp_iters=4, pnp_huber_px=None, pnp_min_pts=6,
                  pnp_weight=0.0, motion=False, motion_len=16, motion_min_frames=3, motion_iters=2, motion_horizon=1,
-                 motion_max_angle=2.0, motion_inverse_rotation=0):
+                 motion_max_angle=2.0, motion_inverse_rotation=0, lm_archive=0, reid_px=None, reid_min_cos=0.5,
+                 lm_arch_min_obs=None):
         self.model = model
         self.sched = PoolSchedule(streams, window, stride, capacity)
         _check_landmarks(landmarks, fuse, carry, track_intrs, self.sched.streams, lm_weight, lm_gate_px)
@@ -1243,7 +1353,10 @@ class StreamPool:
         self._lm = None
         if self.landmarks:
             self._lm = LandmarkMap(window, stride, streams, carry_tracks, list(track_intrs), lm_min_obs, lm_min_pivot,
-                                   lm_inverse_rotation)
+                                   lm_inverse_rotation, lm_archive, reid_px, reid_min_cos, lm_arch_min_obs)
+        elif int(lm_archive):
+            raise ValueError("lm_archive > 0 needs landmarks=True: the archive keeps the landmarks of dead tracks")
+        self.lm_archive = int(lm_archive)
         self.query_fn = query_fn
         self.carry, self.candidate_fn, self.mask_fn = bool(carry), candidate_fn, mask_fn
         _check_warm(warm, self.carry, warm_mode, warm_iters)
@@ -1483,12 +1596,14 @@ class StreamPool:
             rows = self._table(order)[0].long()
             ids, src = ids.index_select(0, rows), src.index_select(0, rows)
         sids = [sid for sid, _ in results]
-        lo, sc, po = _landmark_step(self._lm, sids, tr, sc, self._fused, ids, src, self.lm_weight, self.lm_gate_px,
+        lo, sc, po, ro = _landmark_step(self._lm, sids, tr, sc, self._fused, ids, src, self.lm_weight, self.lm_gate_px,
                                     self._pnp, self._fuser, self._fused_hops)
         self._carry.update(sids, tr, sc)
         results = [(sid, r.with_landmarks(lo, b)) for b, (sid, r) in enumerate(results)]
         if po is not None:
             results = [(sid, r.with_pnp(po, b)) for b, (sid, r) in enumerate(results)]
+        if ro is not None:
+            results = [(sid, r.with_reid(ro, b)) for b, (sid, r) in enumerate(results)]
         return results
 
     @torch.no_grad()

@@ -8,12 +8,12 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "lm_solve.hpp"
 
 namespace comet {
 namespace {
 
 constexpr int LM_THREADS = 256;
-constexpr int LM_ROW = COMET_LM_ROW;  // doubles per accumulator row
 constexpr int LM_MAX_N = COMET_CARRY_MAX_TRACKS;
 
 // Everything below is plain IEEE double evaluated as written (no contraction into fma):
@@ -38,20 +38,6 @@ struct LandmarkArgs {  // by value in the kernel arguments
   int T, N, s, rows, inverse, min_obs;
   double min_pivot;
 };
-
-// rows r1, r2, r3 of the matrix of q (minipytorch3d.quaternion_to_matrix), or of its transpose
-__device__ __forceinline__ void lm_rotation(const float* q, bool inverse, double (&m)[3][3]) {
-  const float4 qf = *reinterpret_cast<const float4*>(q);
-  const double r = qf.x, i = qf.y, j = qf.z, k = qf.w;
-  const double two_s = 2.0 / (r * r + i * i + j * j + k * k);
-  const double m00 = 1.0 - two_s * (j * j + k * k), m01 = two_s * (i * j - k * r), m02 = two_s * (i * k + j * r);
-  const double m10 = two_s * (i * j + k * r), m11 = 1.0 - two_s * (i * i + k * k), m12 = two_s * (j * k - i * r);
-  const double m20 = two_s * (i * k - j * r), m21 = two_s * (j * k + i * r), m22 = 1.0 - two_s * (i * i + j * j);
-  m[0][0] = m00; m[1][1] = m11; m[2][2] = m22;
-  m[0][1] = inverse ? m10 : m01; m[1][0] = inverse ? m01 : m10;
-  m[0][2] = inverse ? m20 : m02; m[2][0] = inverse ? m02 : m20;
-  m[1][2] = inverse ? m21 : m12; m[2][1] = inverse ? m12 : m21;
-}
 
 // row += w (a a^T, a c, c^2) of one equation a . X = c
 __device__ __forceinline__ void lm_add_equation(double (&r)[LM_ROW], double w, const double (&a)[3], double c) {
@@ -129,23 +115,12 @@ __global__ __launch_bounds__(LM_THREADS) void landmark_update_kernel(LandmarkArg
     nobs = (int)r[10];
 
     if (nobs >= a.min_obs) {
-      // M X = g by an unpivoted LDL^T; a pivot at or below min_pivot * max(diag M) is ill-conditioned
-      const double thr = a.min_pivot * fmax(fmax(r[0], r[3]), r[5]);
-      const double d0 = r[0];
-      const double l10 = r[1] / d0, l20 = r[2] / d0;
-      const double d1 = r[3] - l10 * r[1];
-      const double u12 = r[4] - l20 * r[1];
-      const double l21 = u12 / d1;
-      const double d2 = r[5] - l20 * r[2] - l21 * u12;
-      if (d0 <= thr || d1 <= thr || d2 <= thr) {
+      // M X = g by the shared solve (lm_solve.hpp); a pivot at or below min_pivot * max(diag M) is ill-conditioned
+      double sol[3];
+      if (!lm_solve(r, a.min_pivot, sol)) {
         st = 2;
       } else {
-        const double y0 = r[6];
-        const double y1 = r[7] - l10 * y0;
-        const double y2 = r[8] - l20 * y0 - l21 * y1;
-        const double x2 = y2 / d2;
-        const double x1 = y1 / d1 - l21 * x2;
-        const double x0 = y0 / d0 - l10 * x1 - l20 * x2;
+        const double x0 = sol[0], x1 = sol[1], x2 = sol[2];
         // the reprojection on position s, the frame that becomes the next window's first
         const size_t f = (size_t)h * T + s;
         double m[3][3];

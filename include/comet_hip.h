@@ -721,6 +721,74 @@ int comet_landmark_update(const float* tracks, const float* weights, const float
                           int inverse_rotation, int min_obs, double min_pivot, double* X, int32_t* n_obs,
                           float* err_px, int32_t* state, void* stream);
 
+/* comet_landmark_reid (DESIGN.md "Landmark archive"): comet_landmark_update forgets a landmark when its
+ *   track dies. This keeps the row of a dying track in a per-stream archive and hands it back, with its
+ *   identity, to a track born on its projection. One launch per push for the n hops due, after that push's
+ *   comet_pose_fuse and before its comet_landmark_update, on the same stream: grid (n), one workgroup of 256
+ *   threads per hop, no communication between workgroups, no global atomics; the result does not depend on
+ *   the order threads arrive in. Everything is IEEE double evaluated as written (no contraction), and only
+ *   + - * / and sqrt; the solve and the rotation are the text comet_landmark_update uses (csrc/lm_solve.hpp).
+ *   State, next to acc [rows, COMET_LM_ROW] / acc_id [rows] of comet_landmark_update (rows >= S N):
+ *     arch [entries, COMET_LM_ARCH_ROW] f64, entries >= S C, entry e of stream s at s * C + e: 0..11 the
+ *       accumulator row as it was when the track died | 12..14 its solution X | 15..17 the unit view direction
+ *       d = (c - X) / |c - X|, c the camera centre in the body frame when it retired | 18..19 zero.
+ *     arch_id [entries] int32: the landmark's identity, -1 a free entry. arch_cursor [S] int32: the entry the
+ *       next retirement of the stream goes to (a value outside [0, C) is folded into it).
+ *     alias [rows] int32: the archived identity the row was restored from, -1 none.
+ *     S = min(rows / N, entries / C) streams; C = the archive capacity per stream.
+ *   Inputs per hop: tracks [n, T, N, 2] f32, R [n, T, 4] f32, T [n, T, 3] f64, ids / src [n, N] int32,
+ *     stream_idx [n] / intr [n, 4] with their host copies: all as comet_landmark_update takes them. Only window
+ *     position 0 is read: the frame that was position s of the stream's previous window, whose pose is final;
+ *     the last frame a dead track was alive on and the frame a born track's query sits on. Pose: Rm, t as
+ *     comet_landmark_update forms them, x_cam = Rm X + t, c_k = 0 - (Rm_0k t_0 + Rm_1k t_1 + Rm_2k t_2).
+ *     ws [n, N, COMET_LM_ROW] f64: a workspace (the dying rows, so that every read precedes every write).
+ *   Semantics: as if every read of arch, arch_id, acc, acc_id and alias happened before any write.
+ *   1. Dying: acc_id[row] >= 0 and (ids[j] != acc_id[row] or src[j] != j): the rows comet_landmark_update is
+ *      about to overwrite or clear. A dying row is retirable when the shared solve finds no pivot <=
+ *      min_pivot * max(diag M), X is finite, acc[row, 10] >= arch_min_obs and (Rm X + t).z > 0.
+ *   2. Match. A born slot has ids[j] >= 0 and src[j] < 0; its pixel is p = tracks[h, 0, j]. An entry of the
+ *      hop's stream is a candidate when arch_id >= 0, z = (Rm X_e + t).z > 0, d . d' >= reid_min_cos with
+ *      d' = (c - X_e) / |c - X_e| (the sum left to right), and its projection (fx (x / z) + cx, fy (y / z) + cy)
+ *      is finite. dist2 = du du + dv dv, (du, dv) = projection - p widened to double. The pick of a born slot
+ *      with a finite pixel: the candidate of least dist2 among those with dist2 <= reid_px reid_px, ties to
+ *      the lower entry. An entry accepts, of the slots that picked it, the one of least dist2, ties to the
+ *      lower slot. A slot is matched iff its pick accepted it. Entries retired in this launch are no
+ *      candidates in it (a track the score test or the reprojection gate killed is not resurrected in the
+ *      same hop).
+ *   3. Writes. Matched slot j <- entry e: acc[row] = arch[e, 0..11], acc_id[row] = ids[j], alias[row] =
+ *      arch_id[e], arch_id[e] = -1. A carried row (ids[j] >= 0, src[j] == j, acc_id[row] == ids[j]) keeps its
+ *      alias; every other unmatched row: alias[row] = -1. Retirable rows in ascending slot order, r their rank
+ *      (an exclusive prefix sum over the workgroup in chunks of 256 with a carry, as comet_track_carry ranks):
+ *      entry (cursor + r) mod C takes (row, X, d, 0, 0) and the id alias[row] if that is >= 0, else
+ *      acc_id[row]; cursor <- (cursor + count) mod C. Retirements follow the matches: one that lands on an entry
+ *      consumed in this launch reuses it, one that lands on an entry in use overwrites it and is counted, and
+ *      so is one that lands on an entry an earlier retirement of this launch filled (count > C: the last C
+ *      stay).
+ *   Outputs, [n, N]: src_lm int32 = src with src_lm[j] = j for matched slots, which comet_landmark_update takes
+ *     in place of src, so that it adds to the restored row; lm_id int32, the landmark's identity: the row's
+ *     alias after this launch if >= 0, else ids[j] (-1 for a pad); reid_state int32: 0 not a born slot | 1
+ *     matched | 2 no candidate within the gate, or a pixel that is not finite | 3 the pick accepted another
+ *     slot; reid_dist f32 = sqrt(dist2) of a match, +inf otherwise. stats [n, 4] int32 = (retired, matched,
+ *     entries in use afterwards, retirements counted as overwriting).
+ *   LDS: 21 C + 12 N bytes, dynamic (132 KiB at C = N = 4096; a gfx950 workgroup may hold 160 KiB) + 656 B
+ *   static (the pose, the arguments, the scan and the counters).
+ *   COMET_EINVAL before anything is launched, checked in this order: a null pointer, n < 1, N outside
+ *   [1, 4096], C outside [1, COMET_LM_ARCH_MAX], T < 2, rows < n * N, entries < n * C, a host stream index
+ *   outside [0, S) or two equal ones, host intrinsics whose fx or fy is not finite and positive,
+ *   inverse_rotation not 0 or 1, arch_min_obs < 2, min_pivot outside [0, 1), reid_px not finite and positive,
+ *   reid_min_cos outside [-1, 1], tracks / T / intr not 8-B aligned or R / acc / arch / ws not 16-B aligned.
+ *   The kernel range-checks every row and entry index before it addresses memory. */
+#define COMET_LM_ARCH_ROW 20
+#define COMET_LM_ARCH_MAX 4096
+int comet_landmark_reid(const float* tracks, const float* R, const double* T, const int32_t* ids,
+                        const int32_t* src, const int32_t* stream_idx, const int32_t* stream_idx_host,
+                        const double* intr, const double* intr_host, double* acc, int32_t* acc_id,
+                        int32_t* alias, int rows, double* arch, int32_t* arch_id, int32_t* arch_cursor,
+                        int entries, double* ws, int n, int Tw, int N, int C, int inverse_rotation,
+                        int arch_min_obs, double min_pivot, double reid_px, double reid_min_cos,
+                        int32_t* src_lm, int32_t* lm_id, int32_t* reid_state, float* reid_dist,
+                        int32_t* stats, void* stream);
+
 /* comet_landmark_pnp (DESIGN.md "PnP refinement"): the landmarks are 3-D points in the body frame and the
  *   window's tracks their 2-D observations, so every frame of a window has a perspective-n-point problem.
  *   This solves it for every (hop h, window position i) of a push by `iters` Gauss-Newton steps with a

@@ -54,6 +54,9 @@ weights, which converge to nothing meaningful, so it is not an accuracy figure.
 PoseStream(fuse=True, carry=True) objects, landmarks on and off, alternate push by push in one process;
 ms per push of each, the comet_landmark_update launch of a hop alone (20 back-to-back launches / 20), the
 valid landmarks per hop and whether pred_pose_enc stayed identical. A report, not a pass criterion.
+--fuse --carry --landmarks --reid: the landmark archive (comet_landmark_reid, DESIGN.md "Landmark archive"): two
+PoseStream(fuse=True, carry=True, landmarks=True) objects, lm_archive on and off, alternate push by push in
+one process; ms per push of each and the comet_landmark_reid launch of a hop alone. A report.
 --fuse --carry --landmarks --pnp: the PnP refinement (comet_landmark_pnp, DESIGN.md "PnP refinement"): two
 PoseStream(fuse=True, carry=True, landmarks=True) objects, pnp on (report only, pnp_weight 0) and off,
 alternate push by push in one process; ms per push of each, the comet_landmark_pnp launch of a hop alone
@@ -399,6 +402,62 @@ def pnp_bench(model, args, dev, cfg):
         flush=True)
 
 
+def reid_bench(model, args, dev, cfg):
+    """--reid (with --fuse --carry --landmarks): ms per push of PoseStream(fuse, carry, landmarks) with the
+    landmark archive on against off, the two objects alternating push by push in one process with the order
+    rotating, and the comet_landmark_reid launch alone on the hop's own inputs (on a scratch map, so the
+    timed stream's archive is left alone)."""
+    from comet_amd import loop
+    from comet_amd.data import crop_intrinsics
+    from comet_amd.models.utils import INTRINSICS
+    from comet_amd.stream import LandmarkMap, PoseStream, keypoint_candidates
+    T, S, N = args.frames, args.image, args.tracks
+    g = torch.Generator(device=dev).manual_seed(1)
+    total = T + args.warmup + args.hops - 1
+    frames = torch.randn(total, 3, S, S, device=dev, generator=g)
+    sp = loop._keypoint_init(cfg, dev)
+    R0 = torch.tensor([0.8, 0.2, -0.4, 0.4], device=dev)
+    anchor = (R0 / R0.norm(), torch.tensor([331.25, 247.5, 11.375], device=dev), 268.44, 0.5, "AMD")
+    intr = crop_intrinsics(INTRINSICS["AMD"], (0, 0, 2 * S, 2 * S), S)
+    kw = dict(window=T, stride=1, precision=torch.bfloat16, anchor=anchor, fuse=True, carry=True, carry_tracks=N,
+              carry_cell=args.cell, carry_min_score=args.min_score, candidate_fn=keypoint_candidates(sp),
+              landmarks=True, track_intr=intr)
+    objs = {True: PoseStream(model, lm_archive=args.reid_capacity, reid_px=args.reid_px, **kw), False: PoseStream(model, **kw)}
+    scratch = LandmarkMap(T, 1, 1, N, [intr], archive=args.reid_capacity, reid_px=args.reid_px)
+    for o in objs.values():
+        assert o.push(frames[:T - 1]) == []
+    ta, tb, tc, stats, same = [], [], [], [], True
+    for j in range(args.warmup + args.hops):
+        i = j + T - 1
+        order = (True, False) if j % 2 == 0 else (False, True)  # (neither path always runs first)
+        ms, res = {}, {}
+        for f in order:
+            ms[f], res[f] = _timed(lambda: objs[f].push(frames[i]))
+        r = res[True][0]
+        tr, fr, ft = r.pred_tracks.float()[None].contiguous(), r.fused_R[None].contiguous(), r.fused_T[None].contiguous()
+        ids, src = r.track_ids[None].contiguous(), r.track_src[None].contiguous()
+        ms_c, outs = _timed(lambda: [scratch.reidentify([0], tr, fr, ft, ids, src) for _ in range(GATHER_REPS)])
+        scratch.update([0], tr, fr, ft, ids, outs[-1].src_lm)  # (the scratch map lives on: its rows die and retire)
+        if j >= args.warmup:
+            ta.append(ms[True])
+            tb.append(ms[False])
+            tc.append(ms_c / GATHER_REPS)
+            stats.append(objs[True].landmark_map.archive_snapshot(0)[0].numel())
+            same = same and torch.equal(r.pred_pose_enc, res[False][0].pred_pose_enc)
+    a, b, c = statistics.median(ta), statistics.median(tb), statistics.median(tc)
+    print(json.dumps({
+        "metric": f"ms per push, landmark archive on against off, PoseStream fuse + carry + landmarks, T={T} {S}^2 N={N} "
+                  f"C={args.reid_capacity}, bf16, stride 1",
+        "reid_on_ms": round(a, 3), "reid_off_ms": round(b, 3), "on_over_off": round(a / b, 4),
+        "min_reid_on_ms": round(min(ta), 3), "min_reid_off_ms": round(min(tb), 3),
+        "landmark_reid_ms": round(c, 4), "min_landmark_reid_ms": round(min(tc), 4),
+        "landmark_reid_timing": f"device events around {GATHER_REPS} back-to-back launches / {GATHER_REPS}, median over the pushes",
+        "reid_px": args.reid_px, "archived_entries": {"mean": round(statistics.mean(stats), 2), "max": max(stats)},
+        "pred_pose_enc_identical_on_vs_off": same, "pushes": args.hops, "warmup": args.warmup,
+        "data": "synthetic (N(0,1) frames, detector candidates); random-init weights: the landmarks carry no geometry"}),
+        flush=True)
+
+
 def motion_bench(model, args, dev):
     """--motion (with --fuse): ms per push of PoseStream(fuse) with motion on against off, the two objects
     alternating push by push in one process, and the comet_motion_fit launch alone on the hop's own fused
@@ -476,6 +535,10 @@ def main():
                     help="--fuse --carry: time the landmark map (comet_landmark_update) on against off")
     ap.add_argument("--pnp", action="store_true",
                     help="--fuse --carry --landmarks: time the PnP refinement (comet_landmark_pnp) on against off")
+    ap.add_argument("--reid", action="store_true",
+                    help="--fuse --carry --landmarks: time the landmark archive (comet_landmark_reid) on against off")
+    ap.add_argument("--reid-px", type=float, default=2.0, help="--reid: reid_px (not a recommendation)")
+    ap.add_argument("--reid-capacity", type=int, default=4096, help="--reid: lm_archive, entries per stream")
     ap.add_argument("--pnp-huber-px", type=float, default=3.0, help="--pnp: pnp_huber_px (not a recommendation)")
     ap.add_argument("--motion", action="store_true",
                     help="--fuse: time the motion estimate (comet_motion_fit) on against off")
@@ -505,10 +568,15 @@ def main():
         if args.pnp:
             pnp_bench(model, args, dev, cfg)
             return 0
+        if args.reid:
+            reid_bench(model, args, dev, cfg)
+            return 0
         landmark_bench(model, args, dev, cfg)
         return 0
     if args.pnp:
         ap.error("--pnp needs --fuse --carry --landmarks")
+    if args.reid:
+        ap.error("--reid needs --fuse --carry --landmarks")
     if args.carry:
         carry_bench(model, args, dev, cfg)
         return 0
